@@ -16,12 +16,20 @@ xGMI link type / hops, under ``extra.topology``).  ``value``
 = total frames/s of the node (headline phase: ``--route``, default balanced -- frames stay on the
 GPU that produced them unless another shard is starving).
 
+A plain run does only what the headline needs: set-up, the gate, the warmup, the K timed steps, the
+result line.  ``--full`` adds every other measurement the benchmark makes (below: the cross-GPU
+window of an N > 1 run).  ``--dump-outputs DIR`` writes what the LAST timed step handed to its
+caller -- the calibrated frames the consumer took out of the queue (a fixed, seeded sample of their
+pixels) and the peak finder's records, counts and summaries for them -- as ``DIR/<name>.npy``
+(float32 / float64), rows ordered by the frames' index in the raw pool: the pool and the
+calibration constants are seeded, so two runs with the same arguments write the same arrays.
+
 N > 1: every rank is a member of one queue session on torchrun's store and links to every other
-rank through the elastic fabric (csrc/fabric.h).  After the headline window a SECOND fixed-step
-window runs with ``route=remote_only`` (a producer never keeps a frame on its own GPU while a
-consumer on another GPU is linked: every frame crosses xGMI as a HIP-IPC peer copy); its frames/s,
-cross-GPU GB/s and bytes per rank are reported under ``extra.xgmi_phase`` (``--cross-steps 0``
-skips it).  The run is self-validating: it exits non-zero (after printing its line) when a link
+rank through the elastic fabric (csrc/fabric.h).  With ``--full``, after the headline window a SECOND
+fixed-step window runs with ``route=remote_only`` (a producer never keeps a frame on its own GPU
+while a consumer on another GPU is linked: every frame crosses xGMI as a HIP-IPC peer copy); its
+frames/s, cross-GPU GB/s and bytes per rank are reported under ``extra.xgmi_phase``
+(``--cross-steps 0`` skips it).  The run is self-validating: it exits non-zero (after printing its line) when a link
 failed or never attached, when less than 90% of that window's frames crossed GPUs, or when a frame
 arrived with contents that differ from what its producer sent (every 64th frame a producer sends
 to another process carries a content checksum the consumer re-sums from its own ring,
@@ -64,9 +72,16 @@ def parse(argv=None):
                     help="image mode: zero the panel gaps of every frame even in a zero-filled ring (A/B)")
     ap.add_argument("--route", default="balanced", choices=["balanced", "local_first", "spread", "remote_only"],
                     help="routing policy of the headline window")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: for N > 1 the second, route=remote_only "
+                         "window (extra.xgmi_phase).  A plain run sets up, warms up, times --steps steps and prints")
     ap.add_argument("--cross-steps", type=int, default=None,
-                    help="N > 1: steps of the second, route=remote_only window that pushes frames across GPUs over xGMI "
-                         "(default: --steps; 0 skips it)")
+                    help="--full, N > 1: steps of the second, route=remote_only window that pushes frames across GPUs "
+                         "over xGMI (default: --steps; 0 skips it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (sampled calibrated frames, peak "
+                         "records / counts / summaries, ordered by raw-pool index) as DIR/<name>.npy; identical from "
+                         "run to run while --batch is a multiple of --pool-frames (the default)")
     ap.add_argument("--queue-size", type=int, default=None,
                     help="logical (global) queue capacity; default 400 per GPU (README.md:20 example, weak scaling: "
                          "constant queue depth per consumer shard). BASELINE config 3: --gpus 8 --queue-size 400")
@@ -176,6 +191,140 @@ def _copy_stats(samples) -> dict:
             "dev_GB_per_s": round(byts / max(1e-9, sum(dev) * 1e-3) / 1e9, 1),
             "issue_to_done_ms_p50": round(_pct(lat, 0.5), 3), "issue_to_done_ms_p99": round(_pct(lat, 0.99), 3),
             "ms_per_64_frames_dev_p50": round(64 * _pct([d / max(1, f) for d, f in zip(dev, frames)], 0.5), 4)}
+
+
+class OutputDump:
+    """--dump-outputs: what the last timed step hands to its caller.
+
+    The consumer's ring slots are recycled as soon as they are released, so the last step's slots
+    are HELD instead (a batch out of a ring of hundreds): the step runs as every other one, only
+    its releases wait, with a copy of each launch's peak records, counts and summaries (the
+    consumer reuses those buffers).  After the window ``finish`` reads ``SAMPLE`` pixels of every
+    held frame (fixed, seeded indices) and releases the slots; ``save`` writes the arrays.  Rows are
+    ordered by (producer rank, index in that producer's raw pool): event numbers differ from run to
+    run (the steady-state gate takes as many frames as the rate asks for), the pool frame an event
+    cycles through does not.  Bit-identical from run to run except ``peak_summary[:, 1]``, a sum the
+    peak finder accumulates with float atomics (the last bit depends on their order)."""
+
+    SAMPLE = 1 << 17   # pixels per frame: 64 epix10k2M frames -> 33.5 MB of float32
+    MAX_BYTES = 64 << 20
+
+    def __init__(self, directory, ep, consumer, frames: int, pool_frames: int, device):
+        import numpy as np
+        import torch
+
+        self.dir, self.ep, self.consumer, self.pool_frames = directory, ep, consumer, pool_frames
+        view = ep.slot_tensor(0)
+        npix = view.numel()
+        per_frame = 4 * (consumer.params.max_peaks * 8 + 4) if consumer is not None else 0
+        k = min(npix, self.SAMPLE, max(1, (self.MAX_BYTES - (2 << 20)) // max(1, frames) - per_frame) // 4)
+        idx = np.sort(np.random.default_rng(0).choice(npix, size=k, replace=False)) if k < npix else np.arange(npix)
+        self.pixel_index = idx
+        self._idx = torch.from_numpy(idx).to(device)
+        # uint16 (raw mode) has no gather kernel: the same bits as int16
+        self._as = torch.int16 if view.dtype == torch.uint16 else view.dtype
+        self._unsigned = view.dtype == torch.uint16
+        self._frames = torch.zeros((frames, k), dtype=self._as, device=device)
+        self._n = 0
+        self._ids = []
+        # the copies of the launches' records: allocated here, so the timed step allocates nothing
+        self._peaks = self._counts = self._summary = None
+        if consumer is not None:
+            self._peaks = torch.zeros((frames,) + tuple(consumer.peaks.shape[2:]), dtype=consumer.peaks.dtype, device=device)
+            self._counts = torch.zeros((frames,), dtype=consumer.counts.dtype, device=device)
+            self._summary = torch.zeros((frames, 2), dtype=consumer.summary.dtype, device=device)
+        self._m = 0   # frames whose records were copied
+        self._held, self._items = [], []
+        self._release = None
+
+    def hold_item(self, it):
+        """consumer 'none': the step's caller receives the frame itself (released by ``finish``)."""
+        self._items.append(it)
+
+    def arm(self):
+        """Peak-finder consumer: from now on the batches it releases are held, with the records of
+        the launch that read them."""
+        if self.consumer is None or self._release is not None:
+            return
+        import torch
+
+        ep, c = self.ep, self.consumer
+        self._release = ep.release_batch
+
+        def release_batch(slots, stream=None):
+            n = len(slots)
+            b = (c._b - 1) % c._nbuf   # the buffers of the launch that just read these slots
+            m = self._m
+            with torch.cuda.stream(stream):
+                self._peaks[m:m + n].copy_(c.peaks[b, :n])
+                self._counts[m:m + n].copy_(c.counts[b, :n])
+                self._summary[m:m + n].copy_(c.summary[b, :n])
+            self._m += n
+            self._held.append((list(slots), stream))
+
+        ep.release_batch = release_batch
+
+    def disarm(self):
+        if self._release is not None:
+            del self.ep.release_batch   # the instance attribute: the method is back
+            self._release = None
+
+    def _sample(self, view):
+        import torch
+
+        if self._n < self._frames.shape[0]:
+            torch.index_select(view.reshape(-1).view(self._as), 0, self._idx, out=self._frames[self._n])
+            self._n += 1
+
+    def finish(self):
+        """After the window: sample the held frames, then give their slots back."""
+        import torch
+
+        ep = self.ep
+        for slots, stream in self._held:
+            self._ids += [(h.rank, h.idx) for h in ep.pool.headers(slots)]
+            with torch.cuda.stream(stream):
+                for s in slots:
+                    self._sample(ep.slot_tensor(s))
+            ep.release_batch(slots, stream)
+        for it in self._items:
+            self._ids.append((it.rank, it.idx))
+            self._sample(it.data)
+            it.release()
+        self._held, self._items = [], []
+        if ep.gpu:
+            torch.cuda.synchronize(ep.ring.device)
+
+    def save(self, suffix: str = "") -> dict:
+        import numpy as np
+
+        self.finish()
+        os.makedirs(self.dir, exist_ok=True)
+        n = self._n
+        order = sorted(range(n), key=lambda i: (self._ids[i][0], self._ids[i][1] % self.pool_frames, self._ids[i][1]))
+        fr = self._frames[:n].cpu().numpy()
+        if self._unsigned:
+            fr = fr.view(np.uint16)
+        out = {"calib_frames_sample": fr[order].astype(np.float32),
+               "sample_pixel_index": self.pixel_index.astype(np.float64),
+               "frame_pool_index": np.array([self._ids[i][1] % self.pool_frames for i in order], dtype=np.float64),
+               "frame_producer_rank": np.array([self._ids[i][0] for i in order], dtype=np.float64)}
+        if self._peaks is not None and self._m == n:
+            peaks = self._peaks[:n].cpu().numpy()[order]
+            counts = self._counts[:n].cpu().numpy()[order].astype(np.int64)
+            for f in range(n):   # records past the count are stale, and the kernel's record order is not fixed
+                k = min(int(counts[f]), peaks.shape[1])
+                p = peaks[f, :k]
+                peaks[f, :k] = p[np.lexsort(p.T[::-1])]
+                peaks[f, k:] = 0
+            out["peaks"] = peaks.astype(np.float32)
+            out["peak_counts"] = counts.astype(np.float64)
+            out["peak_summary"] = self._summary[:n].cpu().numpy()[order].astype(np.float32)
+        total = 0
+        for name, a in out.items():
+            np.save(os.path.join(self.dir, name + suffix + ".npy"), a)
+            total += a.nbytes
+        return {"dir": self.dir, "frames": n, "bytes": total, "arrays": sorted(out)}
 
 
 def resolve_shape(args, gpu: bool):
@@ -313,6 +462,9 @@ def main(argv=None):
               f"torch.distributed.run with one rank per GPU", file=sys.stderr)
         return 2
     if args.device == "cpu":
+        if args.dump_outputs:
+            print("bench.py: --dump-outputs writes what the GPU path computed; not with --device cpu", file=sys.stderr)
+            return 2
         device = torch.device("cpu")
         numa = None
     else:
@@ -453,9 +605,10 @@ def main(argv=None):
                           name="producer", daemon=True)
     pt.start()
 
-    def consume(n_frames, stall_s=90.0):
+    def consume(n_frames, stall_s=90.0, keep=None):
         """Take n_frames; a rank that receives nothing for stall_s fails loudly instead of hanging the
-        job (a starved consumer would block every barrier after it)."""
+        job (a starved consumer would block every barrier after it).  ``keep``: the OutputDump that
+        holds the frames taken without a consumer engine (--consumer none) instead of releasing them."""
         got = 0
         t_last = time.monotonic()
         while got < n_frames:
@@ -465,7 +618,10 @@ def main(argv=None):
             else:
                 it = ep.get(timeout=0.05)
                 if it is not None:
-                    it.release()
+                    if keep is not None:
+                        keep.hold_item(it)
+                    else:
+                        it.release()
                     got += 1
             if ep.failed is not None:
                 raise RuntimeError(f"queue fabric failed: {ep.failed!r}")
@@ -490,7 +646,7 @@ def main(argv=None):
     # consumer batch issued before it has (both streams were synchronised)
     cstream = (consumer.stream if consumer is not None else torch.cuda.current_stream(device)) if gpu else None
 
-    def window(steps, takes=True, sit_out=False):
+    def window(steps, takes=True, sit_out=False, dump=None):
         """``steps`` timed steps between barriers, in steady state.  Returns (host seconds, max over
         ranks; sustained frames/s of the node = min(sum over producers of the production rate,
         frames consumed / seconds); frames completed by the producers inside the window (sum);
@@ -500,7 +656,8 @@ def main(argv=None):
         for chunks that completed after t0: frames already READY when the window opened are
         excluded, and the rate runs between two chunk completions (utils.metrics.sustained_rate),
         so a short window and a long one measure the same steady state.  ``takes=False``: this rank
-        consumes nothing in the window (a lone producer's own consumer in the remote_only window)."""
+        consumes nothing in the window (a lone producer's own consumer in the remote_only window).
+        ``dump``: the OutputDump that keeps what the window's last step computes."""
         mine = steps * B if takes else 0
         csync()
         barrier()
@@ -508,7 +665,15 @@ def main(argv=None):
         c0 = ep.metrics()
         m0 = prod.clock(cstream) if prod is not None else None
         t0 = time.perf_counter()
-        consume(mine)
+        if dump is not None and mine > 0:
+            consume(mine - B)
+            dump.arm()
+            try:
+                consume(B, keep=dump if consumer is None else None)
+            finally:
+                dump.disarm()
+        else:
+            consume(mine)
         csync()
         if sit_out:
             barrier()   # some rank takes nothing: its window ends when the others' does (every rank calls it)
@@ -591,11 +756,15 @@ def main(argv=None):
     # producers < ranks (BASELINE config 3): every rank's window ends with the slowest consumer's, so
     # the producers' rate and the node's consumption cover the same interval (a producer whose own
     # consumer finished early would otherwise report its rate over a shorter, emptier-queue window)
-    dt, value, produced_window, rate_detail, c0, c1 = window(args.steps, sit_out=n_prod < world)
+    dump = OutputDump(args.dump_outputs, ep, consumer, B, args.pool_frames, device) if args.dump_outputs else None
+    dt, value, produced_window, rate_detail, c0, c1 = window(args.steps, sit_out=n_prod < world, dump=dump)
+    # untimed; N > 1: every rank writes the step it took itself, as <name>_rank<r>.npy
+    dumped = dump.save("" if world == 1 else f"_rank{rank}") if dump is not None else None
 
+    # --full: the measurements the headline does not need
     cross = None
     cross_steps = args.steps if args.cross_steps is None else args.cross_steps
-    if world > 1 and cross_steps > 0:
+    if args.full and world > 1 and cross_steps > 0:
         ep.set_route("remote_only")
         # a LONE producer's own consumer receives nothing under remote_only (no other producer can
         # feed it): it sits the window out and the consumer-only ranks take every frame (BASELINE
@@ -767,6 +936,8 @@ def main(argv=None):
             "links_rank0": linking,
             "topology": topology,
             "steady_gate": gate,
+            "full": bool(args.full),
+            "dumped_outputs_rank0": dumped,
             "staging": staging,
             "staging_copies_span_frame_kernel": copies,
             "numa_node": numa,

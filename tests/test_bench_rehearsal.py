@@ -28,7 +28,7 @@ def test_bench_multirank_cpu(native, nproc, route, producers):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", str(nproc), "--steps", str(steps), "--warmup", "2", "--batch", "4", "--detector", "tiny_epix",
            "--device", "cpu", "--queue-size", str(16 * nproc), "--chunk", "4", "--route", route,
-           "--producers", str(producers)]
+           "--producers", str(producers), "--full"]   # --full: the cross window asserted below
     if producers:
         # config 3 shape: the consumers only take frames (the CPU golden peak finder would be the
         # bottleneck of a CPU rehearsal, not the queue), so the node must consume at the producers' rate
@@ -88,7 +88,7 @@ def test_bench_self_launch_cpu(native, nproc):
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "4", "--warmup", "2",
            "--batch", "4", "--detector", "tiny_epix", "--device", "cpu", "--queue-size", str(16 * nproc),
-           "--chunk", "4"]
+           "--chunk", "4", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

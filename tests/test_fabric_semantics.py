@@ -241,7 +241,12 @@ def test_balanced_feeds_a_starving_consumer_only_rank(native, tok):
         produced = local = remote = 0
         t0 = time.time()
         while time.time() - t0 < 5.0 and remote < 20:
-            produced += _produce(C, pp, 8, produced)
+            # two batches a round, each routed before the next step: the second is offered while the
+            # first is ready in the local consumer (see the two-member test below; one batch a round
+            # needed 4.6 of the 5 s on one busy CPU)
+            for _ in range(2):
+                produced += _produce(C, pp, 8, produced)
+                _wait(lambda: pp.n_produced() == 0, timeout=5.0, what="the fabric to route the batch")
             for pool, is_local in ((pp, True), (cp, False)):
                 while True:   # both consumers take everything they have, at once (fast readers)
                     s = pool.try_get()
@@ -262,7 +267,14 @@ def test_balanced_feeds_a_starving_consumer_only_rank(native, tok):
 def test_balanced_shares_between_two_starving_consumer_only_members(native, tok):
     """Two consumer-only members next to a prosumer: every offer goes to the starving member given
     the fewest in the pass, so neither starves (the first-listed member used to take every offer
-    while it had grants)."""
+    while it had grants).
+
+    balanced feeds a starving member only from a pass that finds frames READY in the prosumer's own
+    consumer (fabric.h kFeedLocalReady).  With one batch per round and local readers that empty
+    their queue at once, such a pass came up only when the fabric thread happened to wake in the
+    middle of a batch -- about 8 times a second, so on a busy machine the 5 s ran out at 21 / 19
+    frames.  Each round therefore commits two batches and waits for the fabric to route each: the
+    second is offered while the first is still ready in the local consumer, every round."""
     C = native
     sb = 128
     pp, _pr, pf = _member(C, tok, 0, 32, 32, sb, 0)    # prosumer, balanced
@@ -277,7 +289,9 @@ def test_balanced_shares_between_two_starving_consumer_only_members(native, tok)
         got = {"local": 0, "a": 0, "b": 0}
         t0 = time.time()
         while time.time() - t0 < 5.0 and min(got["a"], got["b"]) < 20:
-            produced += _produce(C, pp, 8, produced)
+            for _ in range(2):
+                produced += _produce(C, pp, 8, produced)
+                _wait(lambda: pp.n_produced() == 0, timeout=5.0, what="the fabric to route the batch")
             for pool, key in ((pp, "local"), (ap, "a"), (bp, "b")):
                 while True:
                     s = pool.try_get()

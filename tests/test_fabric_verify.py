@@ -20,7 +20,7 @@ def _run_bench(nproc, extra_env, steps=4):
     env.update(extra_env)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", str(steps), "--warmup",
            "2", "--batch", "4", "--detector", "tiny_epix", "--device", "cpu", "--queue-size", str(16 * nproc),
-           "--chunk", "4"]
+           "--chunk", "4", "--full"]   # --full: the window in which every frame crosses processes
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd="/tmp")
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     return r, (json.loads(lines[0]) if lines else None)
@@ -136,7 +136,7 @@ def _run_gpu_bench(nproc, extra_env):
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     env.update(extra_env)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "20", "--warmup", "3",
-           "--source", "device", "--gate-max-s", "3"]
+           "--source", "device", "--gate-max-s", "3", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=200, cwd="/tmp")
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     return r, (json.loads(lines[0]) if lines else None)

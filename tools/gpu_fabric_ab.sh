@@ -25,7 +25,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
     n=$(echo $c | cut -d: -f1); v=$(echo $c | cut -d: -f2); e=$(echo $c | cut -d: -f3 | tr ',' ' ')
     a=$(echo $c | cut -s -d: -f4 | tr ',' ' ')
     cd /tmp/tree_$v || exit 1
-    env $e timeout -k 10 300 python3 bench.py --gpus 2 --steps ${STEPS:-100} --warmup 5 --source ${SRC:-device} \
+    env $e timeout -k 10 300 python3 bench.py --gpus 2 --full --steps ${STEPS:-100} --warmup 5 --source ${SRC:-device} \
       --mode ${MODE:-calib} ${BENCH_ARGS:-} $a > $O/${n}_$r.json 2> $O/${n}_$r.err || { tail -20 $O/${n}_$r.err; exit 1; }
     python3 -c "
 import json; d=json.load(open('$O/${n}_$r.json')); x=d['extra']; c=x['xgmi_phase']; f=x['frame_checks']

@@ -14,7 +14,7 @@ pids=()
 for r in 0 1; do
   RANK=$r WORLD_SIZE=2 LOCAL_RANK=$r LOCAL_WORLD_SIZE=2 MASTER_ADDR=127.0.0.1 MASTER_PORT=$PORT PYTHONPATH=$R \
     timeout -k 10 ${STEP_TIMEOUT:-300} rocprofv3 --kernel-trace --stats --output-format csv -d $O/rank$r -o run -- \
-    python3 $R/bench.py --gpus 2 --steps ${STEPS:-20} --cross-steps ${CROSS_STEPS:-400} --warmup 5 --source device \
+    python3 $R/bench.py --gpus 2 --full --steps ${STEPS:-20} --cross-steps ${CROSS_STEPS:-400} --warmup 5 --source device \
     ${BENCH_ARGS:-} > $O/rank$r.out 2> $O/rank$r.err &
   pids+=($!)
 done

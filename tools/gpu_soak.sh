@@ -13,7 +13,7 @@ export PSANA_RAY_AMD_VERIFY_EVERY=1
 for m in ${MODES:-calib image}; do
   n=${STEPS:-6000}
   [ $m = image ] && n=$((n / 2))
-  timeout -k 10 ${STEP_TIMEOUT:-400} python3 bench.py --gpus 2 --steps $n --cross-steps $n --warmup 10 --source device \
+  timeout -k 10 ${STEP_TIMEOUT:-400} python3 bench.py --gpus 2 --full --steps $n --cross-steps $n --warmup 10 --source device \
     --mode $m > $O/$m.json 2> $O/$m.err
   rc=$?
   # rc 4 = the run completed and found mismatching frames (reported below); anything else ends here

@@ -19,7 +19,7 @@ done
 for c in $CASES; do
   n=$(echo $c | cut -d: -f1); v=$(echo $c | cut -d: -f2); e=$(echo $c | cut -d: -f3 | tr ',' ' ')
   cd /tmp/tree_$v || exit 1
-  env PSANA_RAY_AMD_VERIFY_EVERY=${VERIFY_EVERY:-4} $e timeout -k 10 200 python3 bench.py --gpus 2 --steps ${STEPS:-40} \
+  env PSANA_RAY_AMD_VERIFY_EVERY=${VERIFY_EVERY:-4} $e timeout -k 10 200 python3 bench.py --gpus 2 --full --steps ${STEPS:-40} \
     --warmup 3 --source ${SRC:-device} --mode ${MODE:-calib} --gate-max-s 3 ${BENCH_ARGS:-} > $O/$n.json 2> $O/$n.err
   rc=$?
   case $rc in 0|4) ;; *) echo "$n: rc $rc"; tail -20 $O/$n.err; exit $rc;; esac
