@@ -84,7 +84,9 @@ def main(argv=None):
     results = []
     only = set(a.only.split(",")) if a.only else None
 
-    def report(name, t, nbytes, extra=None):
+    def report(name, t, nbytes, extra=None, frames=None):
+        """frames: the batch that was timed (default: --frames)."""
+        F = a.frames if frames is None else frames
         med, best = t
         r = {"kernel": name, "detector": spec.name, "frames": F, "ms_median": round(med * 1e3, 4),
              "us_per_frame": round(med * 1e6 / F, 3), "frames_per_s": round(F / med, 1),
@@ -150,6 +152,38 @@ def main(argv=None):
                F * npix * 4)
         report("peakfind", timeit(lambda: kernels.peakfind(ol, spec.frame_shape, p, peaks, counts, summ), a.iters),
                F * npix * 4, {"peaks_per_frame": float(counts.float().mean())})
+    if want("radial"):
+        # K-08 radial profile on a 64-frame batch (the consumer's batch) with the geometry bin map,
+        # 1024 bins; the read floor and the peak finder on the SAME frames in the same run
+        from psana_ray_amd.models import RadialBinning, make_geometry
+
+        FR, nb = 64, 1024
+        raw64 = pool.to(dev).repeat((FR + pool.shape[0] - 1) // pool.shape[0], 1, 1, 1)[:FR].contiguous()
+        out64 = torch.empty((FR, *spec.frame_shape), dtype=torch.float32, device=dev)
+        fl = [out64[i] for i in range(FR)]
+        cal.run([raw64[i] for i in range(FR)], fl)
+        rb = RadialBinning.from_geometry(make_geometry(spec), "calib", nb)
+        bins = rb.bins_tensor(dev)
+        rsum = torch.zeros((FR, nb), dtype=torch.int64, device=dev)
+        rcnt = torch.zeros((FR, nb), dtype=torch.int32, device=dev)
+        rprof = torch.zeros((FR, nb), dtype=torch.float32, device=dev)
+        run = torch.zeros(2 * nb + 1, dtype=torch.int64, device=dev)
+        C = _ext.load()
+        fp64 = [int(t.data_ptr()) for t in fl]
+        sums = torch.zeros(FR, dtype=torch.float32, device=dev)
+        p = PeakFinderParams()
+        peaks = torch.empty((FR, p.max_peaks, 8), dtype=torch.float32, device=dev)
+        counts = torch.zeros(FR, dtype=torch.int32, device=dev)
+        summ = torch.zeros((FR, 2), dtype=torch.float32, device=dev)
+        t_read = timeit(lambda: C.read_f32(fp64, npix, 16, False, int(sums.data_ptr()), _ext.stream_handle()), a.iters)
+        report("read_f32 reference (K=16)", t_read, FR * npix * 4, frames=FR)
+        report("peakfind", timeit(lambda: kernels.peakfind(fl, spec.frame_shape, p, peaks, counts, summ), a.iters),
+               FR * npix * 4, frames=FR)
+        t_rad = timeit(lambda: kernels.radial_profile(fl, bins, nb, rsum, rcnt, rprof, -2.0 ** 20, 2.0 ** 20, 8, run=run),
+                       a.iters)
+        report("radial", t_rad, FR * npix * 4 + npix * 2,
+               {"nbins": nb, "pixels_binned_per_frame": float(rcnt.sum(dim=1).float().mean()),
+                "vs_read_floor": round(t_rad[0] / t_read[0], 3)}, frames=FR)
     if want("h2d"):
         C = _ext.load()
         hp = src.pool

@@ -320,6 +320,38 @@ PYBIND11_MODULE(_C, m) {
         py::arg("peaks"), py::arg("counts"), py::arg("summary"), py::arg("total"), py::arg("stream"),
         py::arg("scratch"), py::call_guard<py::gil_scoped_release>());
 
+  m.def("radial",
+        [](const std::vector<uint64_t>& in, int64_t n, uint64_t bins, int nbins, float vmin, float vmax,
+           int frac_bits, uint64_t sums, uint64_t counts, uint64_t profile, uint64_t run, uint64_t stream) {
+          pr::launch_radial(make_ptrs(in, in), (int)in.size(), n, bins, nbins, vmin, vmax, frac_bits, sums, counts,
+                            profile, run, stream);
+        },
+        py::arg("in_ptrs"), py::arg("n"), py::arg("bins"), py::arg("nbins"), py::arg("vmin"), py::arg("vmax"),
+        py::arg("frac_bits"), py::arg("sums"), py::arg("counts"), py::arg("profile"), py::arg("run"),
+        py::arg("stream"),
+        "K-08 radial profile of up to 64 frames: int64 sums / int32 counts / f32 profile [F, nbins] (+ run accumulator)");
+  m.attr("RADIAL_MAX_BINS") = pr::kRadMaxBins;
+  // consumer hot path: ring slots -> radial profiles + run accumulator, one native call
+  m.def("radial_slots",
+        [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int64_t n, uint64_t bins,
+           int nbins, float vmin, float vmax, int frac_bits, uint64_t sums, uint64_t counts, uint64_t profile,
+           uint64_t run, uint64_t stream) {
+          const int ns = (int)slots.size();
+          pr::check(ns >= 1, "radial_slots: no slots");
+          pr::check(slot_bytes >= n * 4, "radial_slots: frame larger than a slot");
+          for (int a = 0; a < ns; a += pr::kMaxFrames) {
+            const int m = std::min(pr::kMaxFrames, ns - a);
+            std::vector<uint64_t> in(m);
+            for (int i = 0; i < m; ++i) in[i] = pool.slot_ptr(slots[a + i]);
+            const uint64_t row = (uint64_t)a * nbins;
+            pr::launch_radial(make_ptrs(in, in), m, n, bins, nbins, vmin, vmax, frac_bits, sums + row * 8,
+                              counts + row * 4, profile + row * 4, run, stream);
+          }
+        },
+        py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("n"), py::arg("bins"), py::arg("nbins"),
+        py::arg("vmin"), py::arg("vmax"), py::arg("frac_bits"), py::arg("sums"), py::arg("counts"),
+        py::arg("profile"), py::arg("run"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+
   m.def("copy_h2d_kernel",
         [](uint64_t dst, uint64_t src, int64_t bytes, int workgroups, uint64_t stream) {
           return pr::launch_copy_h2d(dst, src, bytes, workgroups, stream);

@@ -61,4 +61,11 @@ void launch_peakfind(const FramePtrs& fp, int nframes, int n_panels, int rows, i
                      float son_min, int radius, int max_peaks, uint64_t peaks, uint64_t counts,
                      uint64_t summary, uint64_t total, uint64_t stream,
                      uint64_t scratch = 0);
+// K-08 radial profile (csrc/radial.hip): per-frame int64 sums / int32 counts [F, nbins], float32
+// profiles [F, nbins] and, when run != 0, the run accumulator int64 [2 * nbins + 1] (run_sum,
+// run_count, frames).  bins: uint16 [n], 0xFFFF = excluded, every other entry < nbins (the caller
+// validates the map; the kernel ignores entries >= nbins).  Clears sums / counts on the stream first.
+constexpr int kRadMaxBins = 4096;
+void launch_radial(const FramePtrs& fp, int nframes, int64_t n, uint64_t bins, int nbins, float vmin, float vmax,
+                   int frac_bits, uint64_t sums, uint64_t counts, uint64_t profile, uint64_t run, uint64_t stream);
 }  // namespace pr

@@ -7,7 +7,9 @@ Joins the queue session through :class:`~psana_ray_amd.data_reader.DataReader` (
 the producer, fixing Q-3), reads ``[rank, idx, data, photon_energy]`` items (4 fields, fixing the
 example's 3-field unpack, Q-1) until the explicit end of stream (fixing Q-2), and runs a task:
 ``print`` (the reference example's behaviour), ``peakfind`` (on-GPU K-07 peak finder over
-zero-copy leased batches) or ``none``.  ``--out`` writes the peak lists to an ``.npz``.
+zero-copy leased batches), ``radial`` (on-GPU K-08 azimuthal integration: per-frame radial profiles
+and an exact integer run accumulator) or ``none``.  ``--out`` writes the peak lists / the radial
+accumulator to an ``.npz`` (several consumers' radial files add with ``psana_ray_amd.radial.merge``).
 """
 from __future__ import annotations
 
@@ -32,8 +34,9 @@ def build_parser():
     ap.add_argument("--ray_namespace", type=str, default=DEFAULT_RAY_NAMESPACE)
     ap.add_argument("--queue_name", type=str, default=DEFAULT_QUEUE_NAME)
     ap.add_argument("--device", type=str, default=None)
-    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "train", "none"],
-                    help="train: online PeakNetLite training from peak-finder labels (trainer.py)")
+    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "train", "none"],
+                    help="train: online PeakNetLite training from peak-finder labels (trainer.py); radial: radial "
+                         "profile I(r) / I(q) of every frame + run accumulator (--nbins ... --radial_mask)")
     ap.add_argument("--lr", type=float, default=1e-3, help="--task train: AdamW learning rate")
     ap.add_argument("--save", type=str, default=None, help="--task train: write the model state_dict here")
     ap.add_argument("--ddp", action="store_true",
@@ -48,7 +51,23 @@ def build_parser():
     ap.add_argument("--max_frames", type=int, default=None)
     ap.add_argument("--thr_peak", type=float, default=20.0)
     ap.add_argument("--son_min", type=float, default=5.0)
-    ap.add_argument("--out", type=str, default=None, help="write peaks (npz) when --task peakfind")
+    ap.add_argument("--out", type=str, default=None,
+                    help="write peaks (npz) when --task peakfind; the radial accumulator + per-frame profiles (npz) "
+                         "when --task radial")
+    g = ap.add_argument_group("--task radial")
+    g.add_argument("--nbins", type=int, default=512, help="radial bins (1 .. 4096)")
+    g.add_argument("--center", type=str, default=None, help="beam centre Y,X in image pixels (default: image centre)")
+    g.add_argument("--r_range", type=str, default=None, help="LO,HI of the bins in --unit (default: 0 .. the largest)")
+    g.add_argument("--unit", type=str, default="r_px", choices=["r_px", "q"],
+                   help="bin in pixel radius, or in q = 4 pi sin(theta) / lambda [1/A] (needs --distance_mm and "
+                        "--photon_energy_kev)")
+    g.add_argument("--distance_mm", type=float, default=None, help="sample-detector distance")
+    g.add_argument("--photon_energy_kev", type=float, default=None, help="photon energy of the run (fixed)")
+    g.add_argument("--vmin", type=float, default=None, help="value window: pixels below are ignored (default -2^20)")
+    g.add_argument("--vmax", type=float, default=None, help="value window: pixels above are ignored (default 2^20)")
+    g.add_argument("--radial_mask", type=str, default=None, help="frame-shaped uint8 .npy, 1 = keep")
+    g.add_argument("--detector_name", type=str, default=None,
+                   help="detector of the queue's frames when the session does not name it (older producers)")
     ap.add_argument("--timeout", type=float, default=300.0)
     ap.add_argument("--metrics_interval", type=float, default=10.0, help="seconds between rate lines; 0 disables")
     ap.add_argument("--metrics_json", type=str, default=None, help="append per-interval metrics as JSON lines")
@@ -78,6 +97,107 @@ def resolve_batch(batch=None) -> int:
     from .pipeline import resolve_consumer_batch
 
     return resolve_consumer_batch(batch)
+
+
+def _pair(text, what):
+    try:
+        a, b = (float(x) for x in text.split(","))
+    except ValueError:
+        raise SystemExit(f"{what}: expected two comma-separated numbers, got {text!r}")
+    return a, b
+
+
+def radial_binning(args, detector_name: str, layout: str, frame_shape):
+    """The RadialBinning of ``--task radial`` for a queue of ``layout`` frames of ``detector_name``."""
+    import numpy as np
+
+    from .models import RadialBinning, get_detector, make_geometry
+
+    geo = make_geometry(get_detector(detector_name))
+    mask = np.load(args.radial_mask) if args.radial_mask else None   # allow_pickle stays False
+    rb = RadialBinning.from_geometry(geo, layout, args.nbins,
+                                     center_px=_pair(args.center, "--center") if args.center else None,
+                                     r_range=_pair(args.r_range, "--r_range") if args.r_range else None,
+                                     unit=args.unit, distance_mm=args.distance_mm,
+                                     photon_energy_kev=args.photon_energy_kev, mask=mask)
+    if frame_shape is not None and int(np.prod(frame_shape)) != rb.bins.size:
+        raise ValueError(f"the queue's frames {tuple(frame_shape)} are not {layout} frames of {detector_name} "
+                         f"{rb.frame_shape}")
+    return rb
+
+
+def run_radial(args, reader, stop, progress) -> int:
+    """--task radial: integrate until the end of the stream; ``progress["n"]`` counts frames."""
+    import torch
+
+    from . import radial
+    from .data_reader import DataReaderError, EndOfStream
+    from .pipeline import RadialProfileConsumer
+    from .queue.endpoint import EndOfStream as QueueEOS
+    from .queue.endpoint import QueuePeerError
+
+    cid = reader.consumer_id
+    if reader.endpoint is None:
+        log.error("--task radial needs the distributed queue (a producer session)")
+        return 2
+    if reader.panel_shards > 1:
+        log.error("--task radial: the producers queue panel shards (--panel_shards %d); radial profiles need whole "
+                  "frames (out of scope)", reader.panel_shards)
+        return 2
+    det = (reader.session_meta or {}).get("detector") or {}
+    name = det.get("name") or args.detector_name
+    if not name:
+        log.error("--task radial: the session does not name its detector; pass --detector_name")
+        return 2
+    ring = reader.endpoint.ring
+    cal = reader.calibrator
+    if cal is not None:
+        layout, shape = cal.mode.value, cal.out_shape
+    else:
+        layout, shape = det.get("mode"), tuple(ring.frame_shape)
+        if layout is None:   # --detector_name fallback: tell the layouts apart by the frame shape
+            from .models import get_detector
+
+            layout = "calib" if shape == tuple(get_detector(name).frame_shape) else "image"
+    if layout not in ("calib", "image"):
+        log.error("--task radial: the queue carries %s frames; radial profiles need calibrated ones", layout)
+        return 2
+    try:
+        binning = radial_binning(args, name, layout, shape)
+        cons = RadialProfileConsumer(reader.endpoint, binning, vmin=args.vmin, vmax=args.vmax, batch=args.batch,
+                                     keep_results=bool(args.out), check_ring=cal is None)
+    except (ValueError, KeyError) as e:
+        log.error("--task radial: %s", e)
+        return 2
+    rc = 0
+    try:
+        while not stop["flag"] and (args.max_frames is None or progress["n"] < args.max_frames):
+            left = None if args.max_frames is None else args.max_frames - progress["n"]
+            if cal is None:
+                cons.poll(timeout=1.0, max_items=left)
+            else:   # raw ring (--calibrate_on_read): calibrate here, then integrate
+                items = reader.read_batch(cons.batch if left is None else min(cons.batch, left), timeout=1.0)
+                if items:
+                    meta = [(it.rank, it.idx, it.gevt) for it in items]
+                    frames = reader.calibrate(items)
+                    st = cons.process_frames([frames[i] for i in range(len(items))], meta)
+                    if st is not None:
+                        frames.record_stream(st)
+            progress["n"] = cons.frames
+    except (EndOfStream, QueueEOS):
+        log.info("Consumer %s: end of stream", cid)
+    except (DataReaderError, QueuePeerError) as e:
+        print(f"DataReader error: {e}")
+        print("Queue actor is dead. Exiting...")
+        rc = 1
+    progress["n"] = cons.frames
+    run_sum, run_count, frames = cons.synchronize()
+    print(f"Consumer {cid} radial: frames={frames} nbins={binning.nbins} unit={binning.unit} layout={layout} "
+          f"detector={name} pixels={int(run_count.sum())}", flush=True)
+    if args.out:
+        recs = [(p.cpu().numpy() if isinstance(p, torch.Tensor) else p, m) for p, m in cons.results]
+        radial.save(args.out, binning, cons.vmin, cons.vmax, cons.frac_bits, run_sum, run_count, frames, recs)
+    return rc
 
 
 def main(argv=None) -> int:
@@ -116,6 +236,14 @@ def main(argv=None) -> int:
         reporter = Reporter(registry, rank=cid if cid is not None else 0, interval=args.metrics_interval,
                             json_path=args.metrics_json).start()
         pf = None
+        if args.task == "radial":
+            progress = {"n": 0}
+            registry.register("radial", lambda: {"frames_consumed": progress["n"]})
+            rc = run_radial(args, reader, stop, progress)
+            n = progress["n"]
+            if rc:
+                reporter.stop(final_sample=False)
+                return rc
         if args.task == "peakfind":
             from .ops import kernels
 
@@ -155,7 +283,7 @@ def main(argv=None) -> int:
                 import torch.distributed as dist
 
                 dist.destroy_process_group()
-        while args.task != "train" and not stop["flag"] and (args.max_frames is None or n < args.max_frames):
+        while args.task not in ("train", "radial") and not stop["flag"] and (args.max_frames is None or n < args.max_frames):
             try:
                 if args.task == "peakfind" and reader.endpoint is not None:
                     items = reader.read_batch(args.batch, timeout=1.0)

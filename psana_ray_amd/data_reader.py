@@ -128,6 +128,7 @@ class DataReader:
             sess.close("failed")
             raise
         self._sess, self._queue = sess, ep
+        self._meta = meta
         self._panel_shards = meta.get("panel_shards")
         recipe = meta.get("calibrate_on_read")
         if recipe:
@@ -174,6 +175,11 @@ class DataReader:
                 for it in items:
                     it.release(stream)
         return out
+
+    @property
+    def session_meta(self):
+        """The queue session's metadata as the producers published it (None: in-process queue)."""
+        return getattr(self, "_meta", None)
 
     @property
     def panel_shards(self) -> int:

@@ -1,4 +1,4 @@
-"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07).
+"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07, K-08).
 
 Every wrapper checks device / dtype / shape / contiguity / alignment on the host BEFORE the
 launch (a mis-shaped launch of a hand-written kernel can fault the GPU), splits batches into
@@ -6,6 +6,7 @@ launches of at most ``MAX_FRAMES`` frames, and launches on the given torch strea
 """
 from __future__ import annotations
 
+import operator
 from typing import Optional, Sequence
 
 import torch
@@ -168,6 +169,69 @@ def peakfind(frames: Sequence[torch.Tensor], shape, params, peaks: torch.Tensor,
         C.peakfind([_ptr(t) for t in frames[a:b]], P, H, W, float(params.thr_peak), float(params.son_min),
                    int(params.radius), int(params.max_peaks), _ptr(peaks[a]), _ptr(counts[a:]), _ptr(summary[a]), s,
                    0 if total is None else _ptr(total), 0 if scratch is None else _ptr(scratch))
+
+
+def _validate_bin_map(bins: torch.Tensor, n: int, nbins: int, dev, what: str):
+    """The bin map's shape / dtype / placement, and a one-time (cached on the tensor) check that every
+    entry is < nbins or 0xFFFF."""
+    if bins.dtype != torch.uint16 or bins.dim() != 1 or not bins.is_contiguous() or bins.data_ptr() % 16:
+        raise ValueError(f"{what}: bins must be a contiguous, 16-B aligned 1-D uint16 tensor")
+    if bins.device != dev:
+        raise ValueError(f"{what}: bins on {bins.device}, expected {dev}")
+    if bins.numel() != n:
+        raise ValueError(f"{what}: bin map of {bins.numel()} entries for frames of {n} elements")
+    if getattr(bins, "_pr_checked_nbins", None) == nbins:
+        return
+    b = bins.view(torch.int16).to(torch.int32) & 0xFFFF
+    if bool(((b >= nbins) & (b != 0xFFFF)).any()):
+        raise ValueError(f"{what}: bin map entry >= nbins ({nbins}) that is not 0xFFFF")
+    bins._pr_checked_nbins = nbins
+
+
+def radial_profile(frames: Sequence[torch.Tensor], bins: torch.Tensor, nbins: int, sums: torch.Tensor,
+                   counts: torch.Tensor, profile: torch.Tensor, vmin: float, vmax: float, frac_bits: int,
+                   run: Optional[torch.Tensor] = None, stream=None):
+    """K-08 radial profile (csrc/radial.hip; contract: ops.reference.radial_profile_reference).
+    frames: F float32 tensors of n elements (any layout); bins: uint16 [n] on their device, 0xFFFF =
+    excluded, every other entry < nbins.  Outputs (overwritten): sums int64 [F, nbins], counts int32
+    [F, nbins], profile float32 [F, nbins].  ``run`` (optional): int64 [2 * nbins + 1] on the device --
+    run_sum, run_count, frames -- to which the batch is ADDED (integer atomics: exact, and safe from
+    several streams at once).  Everything is checked here, before any launch."""
+    from .reference import radial_bound_ok
+
+    F = len(frames)
+    try:
+        nbins = operator.index(nbins)   # Python and numpy integers alike
+    except TypeError:
+        raise ValueError(f"radial_profile: nbins must be an integer, got {nbins!r}") from None
+    if not 1 <= nbins <= 4096:
+        raise ValueError(f"radial_profile: nbins must be in [1, 4096], got {nbins}")
+    if not 0 <= int(frac_bits) <= 60:
+        raise ValueError("radial_profile: frac_bits must be in [0, 60]")
+    if not float(vmin) <= float(vmax):
+        raise ValueError("radial_profile: empty value window")
+    if F == 0:
+        return
+    dev = frames[0].device
+    n = frames[0].numel()
+    if not 1 <= n < 2 ** 31:
+        raise ValueError("radial_profile: frames must have 1 .. 2^31 - 1 elements")
+    _check_frames(frames, torch.float32, n, dev, "radial_profile in")
+    if not radial_bound_ok(n, vmin, vmax, frac_bits):
+        raise ValueError(f"radial_profile: max(|vmin|, |vmax|) * 2^frac_bits * n must stay below 2^53 "
+                         f"(window [{vmin}, {vmax}], frac_bits {frac_bits}, {n} elements)")
+    _validate_bin_map(bins, n, nbins, dev, "radial_profile")
+    for t, dt, name in ((sums, torch.int64, "sums"), (counts, torch.int32, "counts"), (profile, torch.float32, "profile")):
+        if t.shape != (F, nbins) or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"radial_profile: {name} must be a contiguous {dt} [F, nbins] tensor on {dev}")
+    if run is not None and (run.dtype != torch.int64 or run.shape != (2 * nbins + 1,) or run.device != dev
+                            or not run.is_contiguous()):
+        raise ValueError("radial_profile: run must be a contiguous int64 [2 * nbins + 1] tensor on the frames' device")
+    C = _ext.load()
+    s = _ext.stream_handle(stream)
+    for a, b in _chunks(F):
+        C.radial([_ptr(t) for t in frames[a:b]], n, _ptr(bins), nbins, float(vmin), float(vmax), int(frac_bits),
+                 _ptr(sums[a]), _ptr(counts[a]), _ptr(profile[a]), 0 if run is None else _ptr(run), s)
 
 
 def mask_frames(frames: Sequence[torch.Tensor], zero: torch.Tensor, stream=None):

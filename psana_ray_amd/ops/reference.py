@@ -190,3 +190,50 @@ def peakfind_reference(frames: torch.Tensor, p: PeakFinderParams):
                            bkg[f, pk, r, c], noise[f, pk, r, c], snr[f, pk, r, c]], dim=1)
         peaks.append(rec)
     return peaks, summary
+
+
+RADIAL_EXCLUDED = 0xFFFF   # bin-map entry of a pixel that never contributes (gap, masked, out of range)
+
+
+def radial_bound_ok(n: int, vmin: float, vmax: float, frac_bits: int) -> bool:
+    """max(|vmin|, |vmax|) * 2^S * n < 2^53: every int64 sum converts to double exactly."""
+    m = max(abs(float(np.float32(vmin))), abs(float(np.float32(vmax))))   # the window as the kernel sees it
+    return bool(np.isfinite(m)) and m * (2.0 ** int(frac_bits)) * int(n) < 2.0 ** 53
+
+
+def radial_profile_reference(frames: torch.Tensor, bins, nbins: int, vmin: float, vmax: float, frac_bits: int):
+    """K-08 golden: radial profiles by exact INTEGER accumulation.  ``frames``: [F, ...] float32 (any
+    frame layout of n elements), ``bins``: uint16 [n] (0xFFFF = excluded, else < nbins).  A pixel
+    contributes iff its bin is not 0xFFFF and vmin <= v <= vmax (NaN fails, +-inf is outside); it adds
+    q = int64(round_half_even(v * 2^S)) to sum[f, bin] and 1 to count[f, bin].  Returns (sum int64
+    [F, nbins], count int32 [F, nbins], profile float32 [F, nbins] = float32(double(sum) * 2^-S /
+    double(count)), +0 where count == 0)."""
+    F = frames.shape[0]
+    x = frames.reshape(F, -1).to(torch.float32).cpu()
+    n = x.shape[1]
+    b = torch.as_tensor(np.asarray(bins.cpu() if isinstance(bins, torch.Tensor) else bins).reshape(-1).astype(np.int64))
+    if b.numel() != n:
+        raise ValueError(f"radial: bin map of {b.numel()} entries for frames of {n} elements")
+    if not 1 <= int(nbins) <= 4096:
+        raise ValueError("radial: nbins must be in [1, 4096]")
+    if not radial_bound_ok(n, vmin, vmax, frac_bits):
+        raise ValueError("radial: max(|vmin|, |vmax|) * 2^frac_bits * n must stay below 2^53")
+    inb = b != RADIAL_EXCLUDED
+    if bool((b[inb] >= nbins).any()) or bool((b < 0).any()):
+        raise ValueError("radial: bin map entry >= nbins")
+    lo, hi = np.float32(vmin), np.float32(vmax)
+    ok = inb.unsqueeze(0) & (x >= float(lo)) & (x <= float(hi))
+    q = torch.where(ok, torch.round(x * float(2 ** int(frac_bits))), torch.zeros_like(x)).to(torch.int64)
+    idx = torch.where(inb, b, torch.zeros_like(b))
+    sums = torch.zeros((F, nbins), dtype=torch.int64)
+    counts = torch.zeros((F, nbins), dtype=torch.int64)
+    sums.index_add_(1, idx, q)
+    counts.index_add_(1, idx, ok.to(torch.int64))
+    return sums, counts.to(torch.int32), radial_profile_from_sums(sums, counts, frac_bits)
+
+
+def radial_profile_from_sums(sums: torch.Tensor, counts: torch.Tensor, frac_bits: int) -> torch.Tensor:
+    """float32(double(sum) * 2^-S / double(count)), +0 where count == 0."""
+    c = counts.to(torch.float64)
+    mean = sums.to(torch.float64) * (2.0 ** -int(frac_bits)) / torch.where(c > 0, c, torch.ones_like(c))
+    return torch.where(c > 0, mean, torch.zeros_like(mean)).to(torch.float32)

@@ -12,7 +12,8 @@ Producer (replaces psana_ray/producer.py:78-117, ``produce_data``):
   * frames are written straight into the destination slot (no intermediate copies).
 
 Consumer: drains this rank's shard in batches and runs the on-GPU peak finder (K-07) on a
-consumer stream, releasing slots stream-ordered (BASELINE config 5).
+consumer stream, releasing slots stream-ordered (BASELINE config 5); RadialProfileConsumer runs the
+radial profile (K-08) the same way and keeps an exact integer run accumulator on the device.
 """
 from __future__ import annotations
 
@@ -612,3 +613,180 @@ class PeakFinderConsumer:
             self.sync_streams()
             self.peaks_total = int(self.count_acc.item())
         return self.peaks_total
+
+
+class RadialProfileConsumer:
+    """Consumer engine: batches of leased slots -> K-08 radial profile (csrc/radial.hip) ->
+    stream-ordered release.  Same surface and stream scheme as :class:`PeakFinderConsumer`.
+
+    Per frame: int64 sums / int32 counts / float32 profile ``[nbins]``; per run: the integer
+    accumulator ``run_sum`` / ``run_count`` / ``frames`` kept on the device (added to by both consumer
+    streams with integer atomics -- exact in any order) and brought to the host by
+    :meth:`synchronize`.  CPU endpoints run the golden model (ops.reference)."""
+
+    def __init__(self, endpoint: QueueEndpoint, binning, vmin: Optional[float] = None, vmax: Optional[float] = None,
+                 frac_bits: Optional[int] = None, batch: Optional[int] = None, keep_results: bool = False,
+                 stream_kind: str = CONSUMER_STREAM_KIND, streams: int = CONSUMER_STREAMS,
+                 ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
+        """check_ring=False: the queue carries RAW frames that the caller calibrates before
+        :meth:`process_frames` (``--calibrate_on_read``), so the ring's frame shape is not the binning's."""
+        from .models import radial as _radial
+        from .ops.reference import radial_bound_ok
+
+        self.ep = endpoint
+        self.binning = binning
+        self.nbins = int(binning.nbins)
+        self.vmin = _radial.DEFAULT_VMIN if vmin is None else float(vmin)
+        self.vmax = _radial.DEFAULT_VMAX if vmax is None else float(vmax)
+        self.frac_bits = _radial.DEFAULT_FRAC_BITS if frac_bits is None else int(frac_bits)
+        self.batch = min(resolve_consumer_batch(batch, ranks_per_gpu), kernels.MAX_FRAMES)
+        self.device = endpoint.ring.device
+        self.gpu = self.device.type == "cuda"
+        self.n = int(binning.bins.size)
+        if check_ring and int(np.prod(endpoint.ring.frame_shape)) != self.n:
+            raise ValueError(f"radial: binning of {self.n} elements ({binning.layout} layout) for queue frames "
+                             f"{tuple(endpoint.ring.frame_shape)}")
+        if not self.vmin <= self.vmax or not 0 <= self.frac_bits <= 60:
+            raise ValueError("radial: empty value window or frac_bits outside [0, 60]")
+        if not radial_bound_ok(self.n, self.vmin, self.vmax, self.frac_bits):
+            raise ValueError("radial: max(|vmin|, |vmax|) * 2^frac_bits * n must stay below 2^53")
+        self.frames = 0
+        self.keep_results = keep_results
+        # per batch: (profiles [n, nbins] f32 on the HOST -- pinned, filled asynchronously on the GPU
+        # path: read them after sync_streams() / synchronize() --, [(rank, idx, gevt), ...])
+        self.results = []
+        self.run_sum = np.zeros(self.nbins, np.int64)
+        self.run_count = np.zeros(self.nbins, np.int64)
+        self.run_frames = 0
+        if self.gpu:
+            self.streams = _make_streams(self.device, int(streams), stream_kind, owner=self)
+            self.stream = self.streams[0]
+            B, nb = self.batch, self.nbins
+            self._nbuf = 2 * len(self.streams)   # buffer k % nbuf is reused by launch k + nbuf, on k's stream
+            self.sums = torch.zeros((self._nbuf, B, nb), dtype=torch.int64, device=self.device)
+            self.counts = torch.zeros((self._nbuf, B, nb), dtype=torch.int32, device=self.device)
+            self.profile = torch.zeros((self._nbuf, B, nb), dtype=torch.float32, device=self.device)
+            self.run = torch.zeros(2 * nb + 1, dtype=torch.int64, device=self.device)
+            self.bins = binning.bins_tensor(self.device)
+            kernels._validate_bin_map(self.bins, self.n, nb, self.device, "radial")
+            self._b = 0
+        else:
+            self._bins_cpu = torch.from_numpy(binning.bins.astype(np.int64))
+
+    def _keep(self, b: int, n: int, meta):
+        """keep_results, GPU: the batch's profiles go to PINNED HOST memory by an asynchronous copy on
+        the current (consumer) stream, so a long run keeps nothing in HBM (64 frames x 1024 bins =
+        256 KiB of host memory per batch).  The kept tensors are valid after :meth:`sync_streams`."""
+        host = torch.empty((n, self.nbins), dtype=torch.float32, pin_memory=True)
+        host.copy_(self.profile[b, :n], non_blocking=True)
+        self.results.append((host, meta))
+
+    def _next(self):
+        b = self._b % self._nbuf
+        k = self._b % len(self.streams)
+        self._b += 1
+        return b, self.streams[k]
+
+    def process_frames(self, frames, meta):
+        """Integrate ``frames`` (tensors of n elements on this consumer's device, issued on the current
+        stream) that are not queue items -- e.g. frames calibrated on read.  ``meta``: their
+        ``(rank, idx, gevt)``.  GPU: returns the consumer stream the batch runs on."""
+        n = len(frames)
+        if n == 0:
+            return None
+        st = None
+        if self.gpu:
+            b, st = self._next()
+            st.wait_stream(torch.cuda.current_stream(self.device))   # the frames were produced / leased on it
+            with torch.cuda.stream(st):
+                kernels.radial_profile(list(frames), self.bins, self.nbins, self.sums[b, :n], self.counts[b, :n],
+                                       self.profile[b, :n], self.vmin, self.vmax, self.frac_bits, run=self.run,
+                                       stream=st)
+                if self.keep_results:
+                    self._keep(b, n, list(meta))
+        else:
+            from .ops import reference
+
+            s, c, prof = reference.radial_profile_reference(torch.stack([t.reshape(-1) for t in frames]),
+                                                            self._bins_cpu, self.nbins, self.vmin, self.vmax,
+                                                            self.frac_bits)
+            self.run_sum += s.sum(dim=0).numpy()
+            self.run_count += c.to(torch.int64).sum(dim=0).numpy()
+            self.run_frames += n
+            if self.keep_results:
+                self.results.append((prof, list(meta)))
+        self.frames += n
+        return st
+
+    def process(self, items: List[FrameItem]):
+        if not items:
+            return
+        st = self.process_frames([it.data for it in items], [(it.rank, it.idx, it.gevt) for it in items])
+        for it in items:
+            it.release(st) if self.gpu else it.release()
+
+    def poll(self, timeout: float = 0.05, max_items: Optional[int] = None) -> int:
+        """Take up to ``batch`` ready frames (waiting up to ``timeout`` for the first) and process
+        them.  Returns frames processed; raises EndOfStream at the end of the stream."""
+        n_max = self.batch if max_items is None else max(1, min(self.batch, max_items))
+        if not self.gpu:
+            items: List[FrameItem] = []
+            it = self.ep.get(timeout=timeout)
+            if it is None:
+                return 0
+            items.append(it)
+            while len(items) < n_max:
+                try:
+                    nxt = self.ep.get(timeout=0.0)
+                except EndOfStream:
+                    break
+                if nxt is None:
+                    break
+                items.append(nxt)
+            self.process(items)
+            return len(items)
+        # GPU: one native call to lease, one to integrate (clear, kernel, finalize), one to release
+        st = self.streams[self._b % len(self.streams)]
+        slots = self.ep.get_batch(n_max, timeout, st)
+        n = len(slots)
+        if n == 0:
+            return 0
+        C = _ext.load()
+        b, st = self._next()
+        with trace_range("consumer.radial_batch"):
+            C.radial_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, int(self.bins.data_ptr()), self.nbins,
+                           self.vmin, self.vmax, self.frac_bits, int(self.sums[b].data_ptr()),
+                           int(self.counts[b].data_ptr()), int(self.profile[b].data_ptr()), int(self.run.data_ptr()),
+                           int(st.cuda_stream))
+            if self.keep_results:
+                hs = self.ep.pool.headers(slots)
+                with torch.cuda.stream(st):
+                    self._keep(b, n, [(h.rank, h.idx, h.gevt) for h in hs])
+        self.ep.release_batch(slots, st)
+        self.frames += n
+        return n
+
+    def metrics(self) -> dict:
+        return {"frames_consumed": self.frames}
+
+    def sync_streams(self):
+        """Host waits for every batch issued so far (both consumer streams)."""
+        if self.gpu:
+            for st in self.streams:
+                st.synchronize()
+
+    def synchronize(self):
+        """Wait for every batch and bring the run accumulator to the host.  Returns
+        ``(run_sum int64 [nbins], run_count int64 [nbins], frames)``."""
+        if self.gpu:
+            self.sync_streams()
+            run = self.run.cpu().numpy()
+            self.run_sum, self.run_count = run[:self.nbins].copy(), run[self.nbins:2 * self.nbins].copy()
+            self.run_frames = int(run[2 * self.nbins])
+        return self.run_sum, self.run_count, self.run_frames
+
+    def mean_profile(self) -> np.ndarray:
+        """Run-averaged profile from the (synchronised) accumulator: float32, +0 where no pixel landed."""
+        from .radial import mean_profile
+
+        return mean_profile(self.run_sum, self.run_count, self.frac_bits)

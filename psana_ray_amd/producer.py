@@ -76,8 +76,9 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--data_dir", type=str, default=None, help="raw-run files directory (or $PSANA_RAY_DATA)")
     g.add_argument("--chunk", type=int, default=64, help="frames per H2D copy / kernel launch (<= 64)")
     g.add_argument("--route", type=str, default="balanced", choices=["balanced", "local_first", "spread"])
-    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind"],
-                   help="also consume on every producer rank (co-located consumer, BASELINE config 5)")
+    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial"],
+                   help="also consume on every producer rank (co-located consumer, BASELINE config 5): the K-07 "
+                        "peak finder, or the K-08 radial profile (default binning of psana-ray-consumer)")
     g.add_argument("--producer_slots", type=int, default=None,
                    help="calibrated frames a rank may hold until a consumer takes them (default: its share of "
                         "--queue_size, at least 2 x --chunk)")
@@ -205,7 +206,7 @@ def main(argv=None) -> int:
 
     from .models.detector import Mode
     from .parallel.launch import bind_numa_to_device, detect, device_for
-    from .pipeline import PeakFinderConsumer, ProducerPipeline
+    from .pipeline import PeakFinderConsumer, ProducerPipeline, RadialProfileConsumer
     from .queue.endpoint import EndOfStream, QueueEndpoint
     from .queue.ring import FrameRing, physical_slots
     from .queue.session import QueueSession
@@ -238,6 +239,9 @@ def main(argv=None) -> int:
                       "or a co-located --consumer_task")
             return 2
         mode = Mode.raw   # frames travel raw; DataReader applies read_mode
+    if args.consumer_task == "radial" and (mode == Mode.raw or int(args.panel_shards) > 1):
+        log.error("--consumer_task radial needs whole calibrated frames (not --mode raw / --panel_shards)")
+        return 2
     shards = int(args.panel_shards)
     if shards > 1:
         from .source.shard import PanelShardSource, shard_layout
@@ -311,6 +315,9 @@ def main(argv=None) -> int:
             got = initialize_queue(args.ray_address, args.ray_namespace, args.queue_name, args.queue_size, rank,
                                    size, args.num_consumers, frame_shape, dtype, device.type,
                                    extra={"co_consumers": co_consumer,
+                                          # what the frames are (additive: consumers that need the geometry,
+                                          # --task radial, read it; session compatibility does not)
+                                          "detector": {"name": args.detector_name, "mode": read_mode.value},
                                           "panel_shards": {"n_shards": shards,
                                                            "n_panels": source.full_spec.n_panels,
                                                            "detector_name": args.detector_name}
@@ -348,7 +355,13 @@ def main(argv=None) -> int:
         if co_consumer:
             # batch: config.pipeline_shape for the ranks sharing this GPU (mpirun -n 4 on fewer GPUs
             # takes the shared-GPU shape, like bench.py)
-            cons = PeakFinderConsumer(ep, frame_shape, PeakFinderParams())
+            if args.consumer_task == "radial":
+                from .models import RadialBinning, make_geometry
+
+                geo = getattr(source, "geometry", None) or make_geometry(source.consts.spec)
+                cons = RadialProfileConsumer(ep, RadialBinning.from_geometry(geo, mode, 512))
+            else:
+                cons = PeakFinderConsumer(ep, frame_shape, PeakFinderParams())
             registry.register("consumer", cons.metrics)
 
             def consume():
@@ -357,7 +370,10 @@ def main(argv=None) -> int:
                         cons.poll(timeout=0.1)
                     except EndOfStream:
                         break
-                stats["peaks"] = cons.synchronize()
+                if args.consumer_task == "radial":
+                    stats["radial"] = cons.synchronize()
+                else:
+                    stats["peaks"] = cons.synchronize()
                 stats["consumed"] = cons.frames
 
             cons_thread = threading.Thread(target=consume, name="co-consumer", daemon=True)
@@ -385,8 +401,13 @@ def main(argv=None) -> int:
                          m.get("frames_requeued", 0), m.get("frames_checksummed", 0))
             if cons_thread is not None:
                 cons_thread.join()
-                log.info("Rank %d: co-located consumer processed %d frames, %d peaks", rank,
-                         stats.get("consumed", 0), stats.get("peaks", 0))
+                if args.consumer_task == "radial":
+                    _, run_count, run_frames = stats.get("radial", (None, np.zeros(1, np.int64), 0))
+                    log.info("Rank %d: co-located consumer processed %d frames, radial accumulator of %d frames, "
+                             "%d pixels", rank, stats.get("consumed", 0), run_frames, int(run_count.sum()))
+                else:
+                    log.info("Rank %d: co-located consumer processed %d frames, %d peaks", rank,
+                             stats.get("consumed", 0), stats.get("peaks", 0))
         finally:
             reporter.stop(final_sample=args.metrics_interval > 0 or args.metrics_json is not None)
         return rc
