@@ -4,11 +4,19 @@
 // (figures/psana-ray-architecture.png, README.md:3) and its setup.py:11 names PeakNet as the
 // downstream, but ships no analysis code; this is the consumer-side analysis the framework
 // provides.  Algorithm (peakfinder8-style, simplified, every knob a parameter):
-//   candidate   v > thr_peak and v is the strict local maximum of its (2R+1)^2 window
-//               (ties broken by linear index; pixels outside the panel are absent)
-//   background  mean / population-std of the ring of Chebyshev radius R+1 .. R+2
-//   snr         (v - bkg) / max(noise, 1e-6); kept if snr >= son_min
-//   intensity   sum over the (2R+1)^2 window of (pixel - bkg)
+//   candidate   v > thr_peak and v is the local maximum of its (2R+1)^2 window: v > n for every
+//               neighbour n of lower linear index (dy < 0, or dy == 0 and dx < 0), v >= n for the
+//               others, so of equal values the lowest index wins; pixels outside the panel (the
+//               next row and the next panel in memory included) and NaN pixels are absent
+//   background  the ring of Chebyshev radius R+1 .. R+2, present non-NaN pixels only:
+//               bkg = mean, noise = sqrt(mean((n - bkg)^2)) in a SECOND pass over the ring (the
+//               one-pass s2/nr - bkg^2 cancels in fp32 on an offset background); both 0 when the
+//               ring is empty
+//   snr         (v - bkg) / max(noise, 1e-6); kept iff snr >= son_min (a NaN snr is not kept)
+//   intensity   sum over the present non-NaN pixels of the (2R+1)^2 window of (pixel - bkg)
+//   non-finite  NaN pixels are absent everywhere and never candidates.  +-Inf are ordinary IEEE
+//               values: an Inf in the ring makes noise and snr NaN, which rejects the candidate;
+//               a +Inf pixel is itself a candidate and makes the summary's sum Inf
 // Per-frame summary: number of pixels above thr_peak and their sum (hit-finding statistics),
 // reduced wave -> LDS -> one atomic per workgroup.
 //
@@ -63,7 +71,7 @@ __device__ __forceinline__ bool pf_eval(const At& at, float v, const PfParams& p
       const bool before = (dy < 0) || (dy == 0 && dx < 0);
       if (before ? !(v > n) : !(v >= n)) return false;   // not the strict local max (ties: lower index wins)
     }
-  float s = 0.0f, s2 = 0.0f;
+  float s = 0.0f;
   int nr = 0;
 #pragma unroll
   for (int dy = -H; dy <= H; ++dy)
@@ -74,14 +82,31 @@ __device__ __forceinline__ bool pf_eval(const At& at, float v, const PfParams& p
       const float n = w[dy + H][dx + H];
       if (n != n) continue;
       s += n;
-      s2 += n * n;
       ++nr;
     }
   bkg = nr > 0 ? s / nr : 0.0f;
-  const float var = nr > 0 ? fmaxf(s2 / nr - bkg * bkg, 0.0f) : 0.0f;
-  noise = sqrtf(var);
-  snr = (v - bkg) / fmaxf(noise, 1e-6f);
-  if (snr < pp.son_min) return false;
+  // two-pass variance over the same ring pixels, from the register window: the one-pass form
+  // s2 / nr - bkg^2 cancels in fp32 once the ring sits on an offset of a few hundred sigma
+  // (one running sum: four partial sums by window position measured slower, 1.824 vs 1.754 us/frame
+  // for this form and 1.745-1.750 for the one-pass form, 32 epix10k2M frames,
+  // profiles/peakfind_two_pass/README.md)
+  float ss = 0.0f;
+#pragma unroll
+  for (int dy = -H; dy <= H; ++dy)
+#pragma unroll
+    for (int dx = -H; dx <= H; ++dx) {
+      const int d = max(abs(dy), abs(dx));
+      if (d <= RAD) continue;
+      const float n = w[dy + H][dx + H];
+      if (n != n) continue;
+      const float c = n - bkg;
+      ss += c * c;
+    }
+  // no clamps that would swallow a NaN (fmaxf returns its other operand): an Inf in the ring gives
+  // Inf - Inf = NaN here, which must reach snr and reject the candidate
+  noise = nr > 0 ? sqrtf(ss / nr) : 0.0f;
+  snr = (v - bkg) / (noise < 1e-6f ? 1e-6f : noise);
+  if (!(snr >= pp.son_min)) return false;
 #pragma unroll
   for (int dy = -RAD; dy <= RAD; ++dy)
 #pragma unroll

@@ -159,23 +159,25 @@ def peakfind_reference(frames: torch.Tensor, p: PeakFinderParams):
             before = dy < 0 or (dy == 0 and dx < 0)
             okn = (x > n) if before else (x >= n)
             is_max &= okn | torch.isnan(n)
+    ring = [(dy, dx) for dy in range(-h, h + 1) for dx in range(-h, h + 1) if max(abs(dy), abs(dx)) > R]
     s = torch.zeros_like(x)
-    s2 = torch.zeros_like(x)
     nr = torch.zeros_like(x)
-    for dy in range(-h, h + 1):
-        for dx in range(-h, h + 1):
-            if max(abs(dy), abs(dx)) <= R:
-                continue
-            n = sh(dy, dx)
-            ok = ~torch.isnan(n)
-            n0 = torch.where(ok, n, torch.zeros_like(n))
-            s += n0
-            s2 += n0 * n0
-            nr += ok.to(torch.float32)
+    for dy, dx in ring:
+        n = sh(dy, dx)
+        ok = ~torch.isnan(n)
+        s += torch.where(ok, n, torch.zeros_like(n))
+        nr += ok.to(torch.float32)
     bkg = torch.where(nr > 0, s / nr.clamp(min=1), torch.zeros_like(s))
-    var = torch.where(nr > 0, (s2 / nr.clamp(min=1) - bkg * bkg).clamp(min=0), torch.zeros_like(s))
-    noise = var.sqrt()
-    snr = (x - bkg) / noise.clamp(min=1e-6)
+    # two-pass variance (the one-pass s2/nr - bkg^2 cancels in fp32 on an offset background), and no
+    # clamp at 0: an Inf in the ring gives Inf - Inf = NaN, which reaches snr and rejects the pixel
+    ss = torch.zeros_like(x)
+    for dy, dx in ring:
+        n = sh(dy, dx)
+        c = n - bkg
+        ss += torch.where(torch.isnan(n), torch.zeros_like(n), c * c)
+    noise = torch.where(nr > 0, (ss / nr.clamp(min=1)).sqrt(), torch.zeros_like(s))
+    # NaN-propagating max(noise, 1e-6), written as the kernel writes it
+    snr = (x - bkg) / torch.where(noise < 1e-6, torch.full_like(noise, 1e-6), noise)
     inten = torch.zeros_like(x)
     for dy in range(-R, R + 1):
         for dx in range(-R, R + 1):
