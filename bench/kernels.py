@@ -184,6 +184,36 @@ def main(argv=None):
         report("radial", t_rad, FR * npix * 4 + npix * 2,
                {"nbins": nb, "pixels_binned_per_frame": float(rcnt.sum(dim=1).float().mean()),
                 "vs_read_floor": round(t_rad[0] / t_read[0], 3)}, frames=FR)
+    if want("dark"):
+        # K-09 dark statistics: 64 SEPARATELY allocated raw frames (ring slots are not contiguous) into
+        # zeroed accumulators, and calib_basic on the SAME 64 frames in the same process -- alternating
+        # rounds, the median round of each.  Bytes: the raw frames plus one read-modify-write of the
+        # accumulator planes of every candidate the batch hit (20 B per pixel and candidate, each way).
+        FR, rounds = 64, 5
+        dl = [pool[i % pool.shape[0]].to(dev).clone() for i in range(FR)]
+        dout = torch.empty((FR, *spec.frame_shape), dtype=torch.float32, device=dev)
+        dol = [dout[i] for i in range(FR)]
+        nc, kind = spec.n_candidates, spec.kernel_kind
+        dcnt = torch.zeros((nc, npix), dtype=torch.int32, device=dev)
+        dsum = torch.zeros((nc, npix), dtype=torch.int64, device=dev)
+        dsq = torch.zeros((nc, npix), dtype=torch.int64, device=dev)
+        kernels.dark_accumulate(dl, kind, 0, 65535, dcnt, dsum, dsq)
+        torch.cuda.synchronize()
+        hit = (dcnt.view(nc, -1, 4) != 0).any(dim=2).float().mean(dim=1).tolist()   # per candidate: lanes that RMW
+        for t in (dcnt, dsum, dsq):
+            t.zero_()
+        t_cal, t_dark = [], []
+        for _ in range(rounds):
+            t_cal.append(timeit(lambda: cal.run(dl, dol), a.iters))
+            t_dark.append(timeit(lambda: kernels.dark_accumulate(dl, kind, 0, 65535, dcnt, dsum, dsq), a.iters))
+        mc = sorted(t_cal)[rounds // 2]
+        md = sorted(t_dark)[rounds // 2]
+        report("calib_basic", mc, FR * npix * 6, {"rounds_us_per_frame": [round(t[0] * 1e6 / FR, 3) for t in t_cal]},
+               frames=FR)
+        report("dark", md, FR * npix * 2 + int(sum(hit) * npix * 40),
+               {"rounds_us_per_frame": [round(t[0] * 1e6 / FR, 3) for t in t_dark],
+                "candidate_rmw_fraction": [round(h, 4) for h in hit],
+                "vs_calib_basic": round(md[0] / mc[0], 3)}, frames=FR)
     if want("h2d"):
         C = _ext.load()
         hp = src.pool

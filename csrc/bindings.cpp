@@ -352,6 +352,32 @@ PYBIND11_MODULE(_C, m) {
         py::arg("vmin"), py::arg("vmax"), py::arg("frac_bits"), py::arg("sums"), py::arg("counts"),
         py::arg("profile"), py::arg("run"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
 
+  m.def("dark",
+        [](const std::vector<uint64_t>& in, int64_t n, int kind, int adu_lo, int adu_hi, uint64_t cnt, uint64_t sum,
+           uint64_t sq, uint64_t stream) {
+          pr::launch_dark(make_ptrs(in, in), (int)in.size(), n, kind, adu_lo, adu_hi, cnt, sum, sq, stream);
+        },
+        py::arg("in_ptrs"), py::arg("n"), py::arg("kind"), py::arg("adu_lo"), py::arg("adu_hi"), py::arg("cnt"),
+        py::arg("sum"), py::arg("sq"), py::arg("stream"),
+        "K-09 dark statistics: adds up to 64 raw uint16 frames into cnt int32 / sum int64 / sq int64 [NC, n]");
+  // consumer hot path: ring slots -> dark accumulators, one native call
+  m.def("dark_slots",
+        [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int64_t n, int kind,
+           int adu_lo, int adu_hi, uint64_t cnt, uint64_t sum, uint64_t sq, uint64_t stream) {
+          const int ns = (int)slots.size();
+          pr::check(ns >= 1, "dark_slots: no slots");
+          pr::check(slot_bytes >= n * 2, "dark_slots: frame larger than a slot");
+          for (int a = 0; a < ns; a += pr::kMaxFrames) {
+            const int m = std::min(pr::kMaxFrames, ns - a);
+            std::vector<uint64_t> in(m);
+            for (int i = 0; i < m; ++i) in[i] = pool.slot_ptr(slots[a + i]);
+            pr::launch_dark(make_ptrs(in, in), m, n, kind, adu_lo, adu_hi, cnt, sum, sq, stream);
+          }
+        },
+        py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("n"), py::arg("kind"), py::arg("adu_lo"),
+        py::arg("adu_hi"), py::arg("cnt"), py::arg("sum"), py::arg("sq"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+
   m.def("copy_h2d_kernel",
         [](uint64_t dst, uint64_t src, int64_t bytes, int workgroups, uint64_t stream) {
           return pr::launch_copy_h2d(dst, src, bytes, workgroups, stream);

@@ -68,4 +68,10 @@ void launch_peakfind(const FramePtrs& fp, int nframes, int n_panels, int rows, i
 constexpr int kRadMaxBins = 4096;
 void launch_radial(const FramePtrs& fp, int nframes, int64_t n, uint64_t bins, int nbins, float vmin, float vmax,
                    int frac_bits, uint64_t sums, uint64_t counts, uint64_t profile, uint64_t run, uint64_t stream);
+// K-09 dark statistics (csrc/dark.hip): ADDS up to kMaxFrames raw uint16 frames of n elements into
+// cnt int32 [NC, n], sum int64 [NC, n], sq int64 [NC, n] (NC = 2 / 3 / 1 for kind epix10ka / jungfrau /
+// plain): valid samples with adu_lo <= adu <= adu_hi.  Never clears; one owner thread per pixel, so
+// two launches in flight must not share accumulators.
+void launch_dark(const FramePtrs& fp, int nframes, int64_t n, int kind, int adu_lo, int adu_hi, uint64_t cnt,
+                 uint64_t sum, uint64_t sq, uint64_t stream);
 }  // namespace pr

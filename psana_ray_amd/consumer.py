@@ -8,8 +8,10 @@ the producer, fixing Q-3), reads ``[rank, idx, data, photon_energy]`` items (4 f
 example's 3-field unpack, Q-1) until the explicit end of stream (fixing Q-2), and runs a task:
 ``print`` (the reference example's behaviour), ``peakfind`` (on-GPU K-07 peak finder over
 zero-copy leased batches), ``radial`` (on-GPU K-08 azimuthal integration: per-frame radial profiles
-and an exact integer run accumulator) or ``none``.  ``--out`` writes the peak lists / the radial
-accumulator to an ``.npz`` (several consumers' radial files add with ``psana_ray_amd.radial.merge``).
+and an exact integer run accumulator), ``dark`` (on-GPU K-09 dark-run statistics of a RAW queue:
+per-pixel integer count / sum / sum of squares per gain candidate) or ``none``.  ``--out`` writes the
+peak lists / the radial accumulator / the dark statistics to an ``.npz`` (several consumers' radial
+files add with ``psana_ray_amd.radial.merge``, dark files with ``psana_ray_amd.dark.merge``).
 """
 from __future__ import annotations
 
@@ -34,9 +36,10 @@ def build_parser():
     ap.add_argument("--ray_namespace", type=str, default=DEFAULT_RAY_NAMESPACE)
     ap.add_argument("--queue_name", type=str, default=DEFAULT_QUEUE_NAME)
     ap.add_argument("--device", type=str, default=None)
-    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "train", "none"],
+    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "train", "none"],
                     help="train: online PeakNetLite training from peak-finder labels (trainer.py); radial: radial "
-                         "profile I(r) / I(q) of every frame + run accumulator (--nbins ... --radial_mask)")
+                         "profile I(r) / I(q) of every frame + run accumulator (--nbins ... --radial_mask); dark: "
+                         "per-pixel dark-run statistics of a RAW queue (--adu_min / --adu_max)")
     ap.add_argument("--lr", type=float, default=1e-3, help="--task train: AdamW learning rate")
     ap.add_argument("--save", type=str, default=None, help="--task train: write the model state_dict here")
     ap.add_argument("--ddp", action="store_true",
@@ -53,7 +56,7 @@ def build_parser():
     ap.add_argument("--son_min", type=float, default=5.0)
     ap.add_argument("--out", type=str, default=None,
                     help="write peaks (npz) when --task peakfind; the radial accumulator + per-frame profiles (npz) "
-                         "when --task radial")
+                         "when --task radial; the dark statistics (psana_ray_amd.dark.DarkStats npz) when --task dark")
     g = ap.add_argument_group("--task radial")
     g.add_argument("--nbins", type=int, default=512, help="radial bins (1 .. 4096)")
     g.add_argument("--center", type=str, default=None, help="beam centre Y,X in image pixels (default: image centre)")
@@ -68,6 +71,9 @@ def build_parser():
     g.add_argument("--radial_mask", type=str, default=None, help="frame-shaped uint8 .npy, 1 = keep")
     g.add_argument("--detector_name", type=str, default=None,
                    help="detector of the queue's frames when the session does not name it (older producers)")
+    g = ap.add_argument_group("--task dark")
+    g.add_argument("--adu_min", type=int, default=0, help="ADU window: samples below are ignored (default 0)")
+    g.add_argument("--adu_max", type=int, default=65535, help="ADU window: samples above are ignored (default 65535)")
     ap.add_argument("--timeout", type=float, default=300.0)
     ap.add_argument("--metrics_interval", type=float, default=10.0, help="seconds between rate lines; 0 disables")
     ap.add_argument("--metrics_json", type=str, default=None, help="append per-interval metrics as JSON lines")
@@ -200,6 +206,60 @@ def run_radial(args, reader, stop, progress) -> int:
     return rc
 
 
+def run_dark(args, reader, stop, progress) -> int:
+    """--task dark: accumulate the raw frames' statistics until the end of the stream (they are read
+    as they are: a --calibrate_on_read queue's raw items are NOT calibrated)."""
+    import torch
+
+    from .data_reader import DataReaderError, EndOfStream
+    from .models import get_detector
+    from .pipeline import DarkStatsConsumer
+    from .queue.endpoint import EndOfStream as QueueEOS
+    from .queue.endpoint import QueuePeerError
+
+    cid = reader.consumer_id
+    if reader.endpoint is None:
+        log.error("--task dark needs the distributed queue (a producer session)")
+        return 2
+    if reader.panel_shards > 1:
+        log.error("--task dark: the producers queue panel shards (--panel_shards %d); dark statistics need whole "
+                  "frames (out of scope)", reader.panel_shards)
+        return 2
+    name = ((reader.session_meta or {}).get("detector") or {}).get("name") or args.detector_name
+    if not name:
+        log.error("--task dark: the session does not name its detector; pass --detector_name")
+        return 2
+    if reader.endpoint.ring.dtype != torch.uint16:
+        log.error("--task dark: the queue carries %s frames; dark statistics need raw uint16 ones (a producer with "
+                  "--mode raw or --calibrate_on_read)", str(reader.endpoint.ring.dtype).replace("torch.", ""))
+        return 2
+    try:
+        cons = DarkStatsConsumer(reader.endpoint, get_detector(name), adu_lo=args.adu_min, adu_hi=args.adu_max,
+                                 batch=args.batch)
+    except (ValueError, KeyError) as e:
+        log.error("--task dark: %s", e)
+        return 2
+    rc = 0
+    try:
+        while not stop["flag"] and (args.max_frames is None or progress["n"] < args.max_frames):
+            left = None if args.max_frames is None else args.max_frames - progress["n"]
+            cons.poll(timeout=1.0, max_items=left)
+            progress["n"] = cons.frames
+    except (EndOfStream, QueueEOS):
+        log.info("Consumer %s: end of stream", cid)
+    except (DataReaderError, QueuePeerError) as e:
+        print(f"DataReader error: {e}")
+        print("Queue actor is dead. Exiting...")
+        rc = 1
+    progress["n"] = cons.frames
+    st = cons.stats()
+    print(f"Consumer {cid} dark: frames={st.frames} detector={name} window=[{st.adu_lo},{st.adu_hi}] "
+          f"samples={int(st.cnt.sum())} per_candidate={[int(c) for c in st.cnt.sum(axis=1)]}", flush=True)
+    if args.out:
+        st.save(args.out)
+    return rc
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=getattr(logging, args.log_level), format="%(asctime)s - %(levelname)s - %(message)s")
@@ -244,6 +304,14 @@ def main(argv=None) -> int:
             if rc:
                 reporter.stop(final_sample=False)
                 return rc
+        if args.task == "dark":
+            progress = {"n": 0}
+            registry.register("dark", lambda: {"frames_consumed": progress["n"]})
+            rc = run_dark(args, reader, stop, progress)
+            n = progress["n"]
+            if rc:
+                reporter.stop(final_sample=False)
+                return rc
         if args.task == "peakfind":
             from .ops import kernels
 
@@ -283,7 +351,7 @@ def main(argv=None) -> int:
                 import torch.distributed as dist
 
                 dist.destroy_process_group()
-        while args.task not in ("train", "radial") and not stop["flag"] and (args.max_frames is None or n < args.max_frames):
+        while args.task not in ("train", "radial", "dark") and not stop["flag"] and (args.max_frames is None or n < args.max_frames):
             try:
                 if args.task == "peakfind" and reader.endpoint is not None:
                     items = reader.read_batch(args.batch, timeout=1.0)

@@ -150,6 +150,22 @@ class DataReader:
                           pool_frames=1, data_dir=recipe.get("data_dir"), mode=Mode.raw)
         if getattr(src, "calibrated", False) or not hasattr(src, "consts"):
             raise DataReaderError("calibrate_on_read: the producer's source has no calibration constants here")
+        cf = recipe.get("constants")
+        if cf:   # the producer ran with --constants: the same file, byte for byte, or nothing
+            from .models.constants import CalibConstants, file_sha256
+
+            try:
+                digest = file_sha256(cf["path"])
+            except OSError as e:
+                raise DataReaderError(f"calibrate_on_read: the producer's constants file {cf['path']} cannot be "
+                                      f"read here ({e})") from None
+            if digest != cf["sha256"]:
+                raise DataReaderError(f"calibrate_on_read: constants file {cf['path']} has sha256 {digest}, the "
+                                      f"producer loaded {cf['sha256']}")
+            try:
+                src.consts = CalibConstants.load(cf["path"], src.consts.spec)
+            except ValueError as e:
+                raise DataReaderError(f"calibrate_on_read: {e}") from None
         mask = load_masks(src, recipe.get("uses_bad_pixel_mask", False), recipe.get("manual_mask_path"))
         cm = recipe.get("common_mode")
         cm = None if cm is None else CommonModeParams(int(cm[0]), float(cm[1]), float(cm[2]), int(cm[3]),

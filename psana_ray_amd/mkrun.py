@@ -18,17 +18,19 @@ def main(argv=None) -> int:
     ap.add_argument("--detector_name", required=True)
     ap.add_argument("--num_events", type=int, default=100)
     ap.add_argument("--format", choices=["xtc2", "praw"], default="xtc2")
+    ap.add_argument("--dark", action="store_true",
+                    help="a dark run: no x-rays (no spots, no background photons), pedestal + noise only")
     a = ap.parse_args(argv)
     if a.format == "xtc2":
         from .source.xtc2 import make_synthetic_xtc2_run
 
-        big, smd = make_synthetic_xtc2_run(a.data_dir, a.exp, a.run, a.detector_name, a.num_events)
+        big, smd = make_synthetic_xtc2_run(a.data_dir, a.exp, a.run, a.detector_name, a.num_events, dark=a.dark)
         print(big)
         print(smd)
         return 0
     from .source.rawfile import make_synthetic_run
 
-    p = make_synthetic_run(a.data_dir, a.exp, a.run, a.detector_name, a.num_events)
+    p = make_synthetic_run(a.data_dir, a.exp, a.run, a.detector_name, a.num_events, dark=a.dark)
     print(p)
     return 0
 

@@ -28,6 +28,16 @@ _JF_PED = (3000.0, 14500.0, 15000.0)
 # default common-mode gain set: high / medium gains (epix: FH, FM, AHL-H, AML-M; jungfrau: G0)
 EPIX_CM_GAINS = (0, 1, 3, 4)
 JUNGFRAU_CM_GAINS = (0,)
+CONSTANTS_FORMAT = "psana_ray_amd.constants/1"
+
+
+def file_sha256(path) -> str:
+    """Hex SHA-256 of a file's bytes (what --constants logs and the --calibrate_on_read recipe carries)."""
+    h = hashlib.sha256()
+    with open(str(path), "rb") as f:
+        for block in iter(lambda: f.read(1 << 20), b""):
+            h.update(block)
+    return h.hexdigest()
 
 
 def run_seed(exp: str, run: int, detector: str) -> int:
@@ -84,6 +94,69 @@ class CalibConstants:
                               None if self.gain_config is None else self.gain_config[lo:hi], tuple(self.cm_gains))
 
     # ------------------------------------------------------------------------------------
+    def save(self, path) -> str:
+        """Write the constants to ``path`` (.npz, no pickle): detector name and kind, pedestals, gains,
+        status, gain_config (empty when None) and cm_gains.  :meth:`load` gives every array back bitwise."""
+        path = str(path)
+        cfg = np.zeros(0, np.uint8) if self.gain_config is None else np.asarray(self.gain_config, np.uint8)
+        with open(path, "wb") as f:
+            np.savez(f, format=np.asarray(CONSTANTS_FORMAT), detector=np.asarray(self.spec.name),
+                     kind=np.asarray(self.spec.kind), pedestals=np.asarray(self.pedestals, np.float32),
+                     gains=np.asarray(self.gains, np.float32), status=np.asarray(self.status, np.uint8),
+                     has_gain_config=np.asarray(self.gain_config is not None), gain_config=cfg,
+                     cm_gains=np.asarray(tuple(self.cm_gains), np.int64))
+        return path
+
+    @classmethod
+    def load(cls, path, spec: Optional[DetectorSpec] = None) -> "CalibConstants":
+        """Read a file written by :meth:`save`.  ``spec``: the detector the caller expects (None: the
+        registered detector the file names); a file of another detector kind, another detector name or
+        other array shapes raises ValueError."""
+        from .detector import get_detector
+
+        try:
+            zf = np.load(str(path), allow_pickle=False)
+        except OSError:
+            raise
+        except Exception as e:   # not a zip / npy at all
+            raise ValueError(f"{path}: not a constants file ({e})") from None
+        if not hasattr(zf, "files"):
+            raise ValueError(f"{path}: not a constants file (a bare array)")
+        with zf as z:
+            missing = [k for k in ("format", "detector", "kind", "pedestals", "gains", "status", "has_gain_config",
+                                   "gain_config", "cm_gains") if k not in z.files]
+            if missing:
+                raise ValueError(f"{path}: not a constants file (no {', '.join(missing)})")
+            if str(z["format"]) != CONSTANTS_FORMAT:
+                raise ValueError(f"{path}: constants format {str(z['format'])!r}, expected {CONSTANTS_FORMAT!r}")
+            name, kind = str(z["detector"]), str(z["kind"])
+            ped, gains, status = z["pedestals"], z["gains"], z["status"]
+            cfg = z["gain_config"] if bool(z["has_gain_config"]) else None
+            cmg = tuple(int(g) for g in z["cm_gains"])
+        if spec is None:
+            try:
+                spec = get_detector(name)
+            except KeyError:
+                raise ValueError(f"{path}: constants of the unregistered detector {name!r}; pass its spec") from None
+        if kind != spec.kind or name != spec.name:
+            raise ValueError(f"{path}: constants of {name} ({kind}), expected {spec.name} ({spec.kind})")
+        G, shape = spec.n_gains, tuple(spec.frame_shape)
+        want = {"pedestals": ((G, *shape), np.float32, ped), "gains": ((G, *shape), np.float32, gains),
+                "status": (shape, np.uint8, status)}
+        if spec.kind == "epix10ka":
+            if cfg is None:
+                raise ValueError(f"{path}: epix10ka constants without a gain configuration")
+            want["gain_config"] = (shape, np.uint8, cfg)
+        for k, (shp, dt, arr) in want.items():
+            if tuple(arr.shape) != tuple(shp) or arr.dtype != dt:
+                raise ValueError(f"{path}: {k} is {arr.dtype} {tuple(arr.shape)}, {spec.name} needs "
+                                 f"{np.dtype(dt)} {tuple(shp)}")
+        if cfg is not None and cfg.size and int(cfg.max()) > 4:
+            raise ValueError(f"{path}: gain_config entry outside 0..4")
+        if any(not 0 <= g < G for g in cmg):
+            raise ValueError(f"{path}: cm_gains {cmg} outside the {G} gain ranges of {spec.name}")
+        return cls(spec, ped, gains, status, cfg, cmg)
+
     def create_bad_pixel_mask(self) -> np.ndarray:
         """psana_wrapper.create_bad_pixel_mask() equivalent (producer.py:81): truthy = good."""
         return (self.status == 0).astype(np.uint8)

@@ -1,4 +1,4 @@
-"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07, K-08).
+"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-09).
 
 Every wrapper checks device / dtype / shape / contiguity / alignment on the host BEFORE the
 launch (a mis-shaped launch of a hand-written kernel can fault the GPU), splits batches into
@@ -232,6 +232,60 @@ def radial_profile(frames: Sequence[torch.Tensor], bins: torch.Tensor, nbins: in
     for a, b in _chunks(F):
         C.radial([_ptr(t) for t in frames[a:b]], n, _ptr(bins), nbins, float(vmin), float(vmax), int(frac_bits),
                  _ptr(sums[a]), _ptr(counts[a]), _ptr(profile[a]), 0 if run is None else _ptr(run), s)
+
+
+def validate_dark_window(kind, adu_lo, adu_hi, what: str = "dark_accumulate"):
+    """(kind, adu_lo, adu_hi) as Python ints, or ValueError."""
+    try:
+        kind, adu_lo, adu_hi = operator.index(kind), operator.index(adu_lo), operator.index(adu_hi)
+    except TypeError:
+        raise ValueError(f"{what}: kind and the ADU window must be integers") from None
+    if kind not in (0, 1, 2):
+        raise ValueError(f"{what}: unknown gain kind {kind}")
+    if not 0 <= adu_lo <= adu_hi <= 65535:
+        raise ValueError(f"{what}: the ADU window must satisfy 0 <= lo <= hi <= 65535, got [{adu_lo}, {adu_hi}]")
+    return kind, adu_lo, adu_hi
+
+
+def dark_accumulate(frames: Sequence[torch.Tensor], kind: int, adu_lo: int, adu_hi: int, cnt: torch.Tensor,
+                    sum: torch.Tensor, sq: torch.Tensor, frames_so_far: int = 0, stream=None):
+    """K-09 dark statistics (csrc/dark.hip; contract: ops.reference.dark_accumulate_reference).
+    frames: F raw uint16 tensors of n elements (any layout) on one GPU; ``kind``: DetectorSpec.kernel_kind.
+    ADDS every valid sample with adu_lo <= adu <= adu_hi to cnt int32 [NC, n], sum int64 [NC, n] and
+    sq int64 [NC, n] on the frames' device -- the caller zeroes them once per run and passes in
+    ``frames_so_far`` the frames they already hold (the int32 count bounds a run at 2^31 - 1 frames).
+    One thread owns a pixel and there are no atomics: launches in flight on DIFFERENT streams must
+    not share accumulators.  Everything is checked here, before any launch."""
+    from .reference import DARK_MAX_FRAMES, DARK_NC
+
+    kind, adu_lo, adu_hi = validate_dark_window(kind, adu_lo, adu_hi)
+    F = len(frames)
+    try:
+        frames_so_far = operator.index(frames_so_far)
+    except TypeError:
+        raise ValueError("dark_accumulate: frames_so_far must be an integer") from None
+    if frames_so_far < 0 or frames_so_far + F > DARK_MAX_FRAMES:
+        raise ValueError(f"dark_accumulate: {frames_so_far} + {F} frames would take the run past 2^31 - 1 "
+                         "(the int32 count)")
+    if F == 0:
+        return
+    dev = frames[0].device
+    n = frames[0].numel()
+    if dev.type != "cuda":
+        raise ValueError(f"dark_accumulate: frames on {dev}, expected a GPU")
+    if not 1 <= n < 2 ** 31:
+        raise ValueError("dark_accumulate: frames must have 1 .. 2^31 - 1 elements")
+    _check_frames(frames, torch.uint16, n, dev, "dark_accumulate in")
+    nc = DARK_NC[kind]
+    for t, dt, name in ((cnt, torch.int32, "cnt"), (sum, torch.int64, "sum"), (sq, torch.int64, "sq")):
+        if not isinstance(t, torch.Tensor) or t.shape != (nc, n) or t.dtype != dt or t.device != dev \
+                or not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError(f"dark_accumulate: {name} must be a contiguous, 16-B aligned {dt} [{nc}, {n}] tensor "
+                             f"on {dev}")
+    C = _ext.load()
+    s = _ext.stream_handle(stream)
+    for a, b in _chunks(F):
+        C.dark([_ptr(t) for t in frames[a:b]], n, kind, adu_lo, adu_hi, _ptr(cnt), _ptr(sum), _ptr(sq), s)
 
 
 def mask_frames(frames: Sequence[torch.Tensor], zero: torch.Tensor, stream=None):

@@ -14,6 +14,8 @@ import numpy as np
 import torch
 
 from ..config import CommonModeParams, PeakFinderParams
+from ..dark import MAX_FRAMES as DARK_MAX_FRAMES   # 2^31 - 1 frames per run (the int32 count)
+from ..dark import NC_OF_KIND as DARK_NC           # candidates per kernel kind (epix10ka, jungfrau, plain)
 from ..models.constants import CalibConstants
 from ..models.detector import EPIX_CAND_A, EPIX_CAND_B
 
@@ -239,3 +241,39 @@ def radial_profile_from_sums(sums: torch.Tensor, counts: torch.Tensor, frac_bits
     c = counts.to(torch.float64)
     mean = sums.to(torch.float64) * (2.0 ** -int(frac_bits)) / torch.where(c > 0, c, torch.ones_like(c))
     return torch.where(c > 0, mean, torch.zeros_like(mean)).to(torch.float32)
+
+
+def dark_accumulate_reference(frames: torch.Tensor, kind: int, adu_lo: int, adu_hi: int):
+    """K-09 golden: dark-run statistics by exact INTEGER accumulation.  ``frames``: [F, ...] raw uint16
+    (any frame layout of n elements); ``kind``: DetectorSpec.kernel_kind.  Decode of a raw word r:
+    epix10ka (0) adu = r & 0x3FFF, candidate (r >> 14) & 1, always valid (bit 15 ignored); jungfrau (1)
+    adu = r & 0x3FFF, candidate 0, 1, 2 for gb = r >> 14 = 0, 1, 3, gb == 2 invalid; plain (2) adu = r,
+    candidate 0.  A sample contributes iff it is valid and adu_lo <= adu <= adu_hi (inclusive); it adds
+    1 to cnt[c, p], adu to sum[c, p], adu * adu to sq[c, p].  Returns (cnt int32 [NC, n], sum int64
+    [NC, n], sq int64 [NC, n]) of these frames alone."""
+    kind, adu_lo, adu_hi = int(kind), int(adu_lo), int(adu_hi)
+    if kind not in (0, 1, 2):
+        raise ValueError(f"dark: unknown gain kind {kind}")
+    if not 0 <= adu_lo <= adu_hi <= 65535:
+        raise ValueError(f"dark: the ADU window must satisfy 0 <= lo <= hi <= 65535, got [{adu_lo}, {adu_hi}]")
+    if frames.dtype != torch.uint16:
+        raise ValueError(f"dark: frames must be uint16, got {frames.dtype}")
+    F = frames.shape[0]
+    if F > DARK_MAX_FRAMES:
+        raise ValueError("dark: more than 2^31 - 1 frames")
+    r = frames.cpu().reshape(F, -1).view(torch.int16).to(torch.int64) & 0xFFFF
+    if kind == 0:
+        adu, cand, valid = r & 0x3FFF, (r >> 14) & 1, torch.ones_like(r, dtype=torch.bool)
+    elif kind == 1:
+        gb = r >> 14
+        adu, cand, valid = r & 0x3FFF, torch.where(gb == 3, torch.full_like(gb, 2), gb), gb != 2
+    else:
+        adu, cand, valid = r, torch.zeros_like(r), torch.ones_like(r, dtype=torch.bool)
+    ok = valid & (adu >= adu_lo) & (adu <= adu_hi)
+    cnt, s, q = [], [], []
+    for c in range(DARK_NC[kind]):
+        m = (ok & (cand == c)).to(torch.int64)
+        cnt.append(m.sum(dim=0))
+        s.append((m * adu).sum(dim=0))
+        q.append((m * adu * adu).sum(dim=0))
+    return torch.stack(cnt).to(torch.int32), torch.stack(s), torch.stack(q)

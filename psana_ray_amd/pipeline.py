@@ -790,3 +790,158 @@ class RadialProfileConsumer:
         from .radial import mean_profile
 
         return mean_profile(self.run_sum, self.run_count, self.frac_bits)
+
+
+class DarkStatsConsumer:
+    """Consumer engine: batches of leased RAW uint16 slots -> K-09 dark statistics (csrc/dark.hip) ->
+    stream-ordered release.  Same surface and stream scheme as :class:`RadialProfileConsumer`.
+
+    Per run: per-pixel, per-candidate count / sum / sum of squares of the raw ADU inside the window
+    ``[adu_lo, adu_hi]`` -- integers, so the result is exact in any frame order.  The kernel owns a
+    pixel per launch and uses no atomics, so every consumer stream has its OWN accumulator set (two
+    streams never read-modify-write the same words); :meth:`synchronize` adds the sets on the host.
+    CPU endpoints run the golden model (ops.reference)."""
+
+    def __init__(self, endpoint: QueueEndpoint, spec, adu_lo: int = 0, adu_hi: Optional[int] = None,
+                 batch: Optional[int] = None, stream_kind: str = CONSUMER_STREAM_KIND,
+                 streams: int = CONSUMER_STREAMS, ranks_per_gpu: Optional[int] = None):
+        from .ops.reference import DARK_MAX_FRAMES
+
+        self.ep = endpoint
+        self.spec = spec
+        self.kind, self.adu_lo, self.adu_hi = kernels.validate_dark_window(
+            spec.kernel_kind, adu_lo, 65535 if adu_hi is None else adu_hi, "dark")
+        self.nc = int(spec.n_candidates)
+        self.n = int(spec.npix)
+        self.batch = min(resolve_consumer_batch(batch, ranks_per_gpu), kernels.MAX_FRAMES)
+        self.device = endpoint.ring.device
+        self.gpu = self.device.type == "cuda"
+        if endpoint.ring.dtype != torch.uint16:
+            raise ValueError(f"dark: the queue carries {endpoint.ring.dtype} frames, dark statistics need raw uint16")
+        if int(np.prod(endpoint.ring.frame_shape)) != self.n:
+            raise ValueError(f"dark: queue frames {tuple(endpoint.ring.frame_shape)} are not the {self.n} pixels "
+                             f"of {spec.name}")
+        self.max_frames = DARK_MAX_FRAMES
+        self.frames = 0
+        self.cnt = np.zeros((self.nc, self.n), np.int64)
+        self.sum = np.zeros((self.nc, self.n), np.int64)
+        self.sq = np.zeros((self.nc, self.n), np.int64)
+        if self.gpu:
+            self.streams = _make_streams(self.device, int(streams), stream_kind, owner=self)
+            self.stream = self.streams[0]
+            # one accumulator set per stream; set k is only ever touched by launches on stream k
+            self._acc = [(torch.zeros((self.nc, self.n), dtype=torch.int32, device=self.device),
+                          torch.zeros((self.nc, self.n), dtype=torch.int64, device=self.device),
+                          torch.zeros((self.nc, self.n), dtype=torch.int64, device=self.device))
+                         for _ in self.streams]
+            self._b = 0
+
+    def _check_bound(self, n: int):
+        if self.frames + n > self.max_frames:
+            raise ValueError(f"dark: {self.frames} + {n} frames would take the run past 2^31 - 1 (the int32 count)")
+
+    def _next(self):
+        k = self._b % len(self.streams)
+        self._b += 1
+        return k, self.streams[k]
+
+    def process_frames(self, frames, meta=None):
+        """Add ``frames`` (raw uint16 tensors of n elements on this consumer's device, issued on the
+        current stream) that are not queue items.  GPU: returns the consumer stream the batch runs on."""
+        n = len(frames)
+        if n == 0:
+            return None
+        self._check_bound(n)
+        st = None
+        if self.gpu:
+            k, st = self._next()
+            cnt, s, q = self._acc[k]
+            st.wait_stream(torch.cuda.current_stream(self.device))   # the frames were produced / leased on it
+            with torch.cuda.stream(st):
+                kernels.dark_accumulate(list(frames), self.kind, self.adu_lo, self.adu_hi, cnt, s, q,
+                                        frames_so_far=self.frames, stream=st)
+        else:
+            from .ops import reference
+
+            c, s, q = reference.dark_accumulate_reference(torch.stack([t.reshape(-1) for t in frames]), self.kind,
+                                                          self.adu_lo, self.adu_hi)
+            self.cnt += c.numpy()
+            self.sum += s.numpy()
+            self.sq += q.numpy()
+        self.frames += n
+        return st
+
+    def process(self, items: List[FrameItem]):
+        if not items:
+            return
+        st = self.process_frames([it.data for it in items])
+        for it in items:
+            it.release(st) if self.gpu else it.release()
+
+    def poll(self, timeout: float = 0.05, max_items: Optional[int] = None) -> int:
+        """Take up to ``batch`` ready frames (waiting up to ``timeout`` for the first) and add them.
+        Returns frames processed; raises EndOfStream at the end of the stream."""
+        n_max = self.batch if max_items is None else max(1, min(self.batch, max_items))
+        n_max = max(1, min(n_max, self.max_frames - self.frames))
+        self._check_bound(1)
+        if not self.gpu:
+            items: List[FrameItem] = []
+            it = self.ep.get(timeout=timeout)
+            if it is None:
+                return 0
+            items.append(it)
+            while len(items) < n_max:
+                try:
+                    nxt = self.ep.get(timeout=0.0)
+                except EndOfStream:
+                    break
+                if nxt is None:
+                    break
+                items.append(nxt)
+            self.process(items)
+            return len(items)
+        # GPU: one native call to lease, one to accumulate, one to release
+        st = self.streams[self._b % len(self.streams)]
+        slots = self.ep.get_batch(n_max, timeout, st)
+        n = len(slots)
+        if n == 0:
+            return 0
+        C = _ext.load()
+        k, st = self._next()
+        cnt, s, q = self._acc[k]
+        with trace_range("consumer.dark_batch"):
+            C.dark_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.kind, self.adu_lo, self.adu_hi,
+                         int(cnt.data_ptr()), int(s.data_ptr()), int(q.data_ptr()), int(st.cuda_stream))
+        self.ep.release_batch(slots, st)
+        self.frames += n
+        return n
+
+    def metrics(self) -> dict:
+        return {"frames_consumed": self.frames}
+
+    def sync_streams(self):
+        """Host waits for every batch issued so far (all consumer streams)."""
+        if self.gpu:
+            for st in self.streams:
+                st.synchronize()
+
+    def synchronize(self):
+        """Wait for every batch and add the per-stream accumulator sets on the host (exact).  Returns
+        ``(cnt int64 [NC, n], sum int64 [NC, n], sq int64 [NC, n], frames)``."""
+        if self.gpu:
+            self.sync_streams()
+            self.cnt = np.zeros((self.nc, self.n), np.int64)
+            self.sum = np.zeros((self.nc, self.n), np.int64)
+            self.sq = np.zeros((self.nc, self.n), np.int64)
+            for cnt, s, q in self._acc:
+                self.cnt += cnt.cpu().numpy().astype(np.int64)
+                self.sum += s.cpu().numpy()
+                self.sq += q.cpu().numpy()
+        return self.cnt, self.sum, self.sq, self.frames
+
+    def stats(self):
+        """The (synchronised) run as a :class:`psana_ray_amd.dark.DarkStats`."""
+        from .dark import DarkStats
+
+        cnt, s, q, frames = self.synchronize()
+        return DarkStats(self.spec.name, self.kind, self.adu_lo, self.adu_hi, frames, cnt.copy(), s.copy(), q.copy())

@@ -18,6 +18,7 @@ from __future__ import annotations
 import argparse
 import logging
 import math
+import os
 import signal
 import sys
 import threading
@@ -76,9 +77,15 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--data_dir", type=str, default=None, help="raw-run files directory (or $PSANA_RAY_DATA)")
     g.add_argument("--chunk", type=int, default=64, help="frames per H2D copy / kernel launch (<= 64)")
     g.add_argument("--route", type=str, default="balanced", choices=["balanced", "local_first", "spread"])
-    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial"],
+    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark"],
                    help="also consume on every producer rank (co-located consumer, BASELINE config 5): the K-07 "
-                        "peak finder, or the K-08 radial profile (default binning of psana-ray-consumer)")
+                        "peak finder, the K-08 radial profile (default binning of psana-ray-consumer), or the K-09 "
+                        "dark statistics (needs --mode raw; --out_dark writes the file)")
+    g.add_argument("--out_dark", type=str, default=None,
+                   help="--consumer_task dark: write the rank's dark statistics (psana_ray_amd.dark.DarkStats .npz) here")
+    g.add_argument("--constants", type=str, default=None,
+                   help="calibration constants file (CalibConstants.save / python -m psana_ray_amd.dark derive) that "
+                        "replaces the source's own constants; synthetic, XTC2 and raw-file sources")
     g.add_argument("--producer_slots", type=int, default=None,
                    help="calibrated frames a rank may hold until a consumer takes them (default: its share of "
                         "--queue_size, at least 2 x --chunk)")
@@ -167,7 +174,7 @@ def _read_recipe(args, read_mode, read_cm) -> dict:
             "common_mode": None if read_cm is None else [read_cm.flags, read_cm.thr, read_cm.maxcorr,
                                                           read_cm.npix_min, read_cm.bank_cols],
             "uses_bad_pixel_mask": bool(args.uses_bad_pixel_mask), "manual_mask_path": args.manual_mask_path,
-            "data_dir": args.data_dir}
+            "data_dir": args.data_dir, "constants": getattr(args, "constants_recipe", None)}
 
 
 def produce_data(pipeline, max_steps=None, stop=None):
@@ -179,6 +186,29 @@ def produce_data(pipeline, max_steps=None, stop=None):
     except QueuePeerError:
         log.error("Rank %d: Queue fabric failed. Exiting...", pipeline.rank)   # producer.py:113
         return pipeline.frames
+
+
+def apply_constants_file(args, source, rank: int = 0) -> bool:
+    """--constants: replace ``source.consts`` by the file's constants (before panel sharding, masks and the
+    Calibrator read them).  Logs the file and its SHA-256 and leaves ``args.constants_recipe`` (absolute
+    path + hash) for the --calibrate_on_read recipe.  False, after logging why, when the source is a
+    psana_wrapper one or the file does not fit the detector."""
+    from .models.constants import CalibConstants, file_sha256
+    from .source import PsanaWrapperSource
+
+    if isinstance(source, PsanaWrapperSource) or getattr(source, "consts", None) is None:
+        log.error("--constants does not apply to a psana_wrapper source (its constants come from psana; out of scope)")
+        return False
+    path = os.path.abspath(args.constants)
+    try:
+        digest = file_sha256(path)
+        source.consts = CalibConstants.load(path, source.consts.spec)
+    except (OSError, ValueError) as e:
+        log.error("--constants: %s", e)
+        return False
+    args.constants_recipe = {"path": path, "sha256": digest}
+    log.info("Rank %d: calibration constants from %s (sha256 %s)", rank, path, digest)
+    return True
 
 
 def build_calibrator(source, device, mode, mask, common_mode_text):
@@ -206,7 +236,7 @@ def main(argv=None) -> int:
 
     from .models.detector import Mode
     from .parallel.launch import bind_numa_to_device, detect, device_for
-    from .pipeline import PeakFinderConsumer, ProducerPipeline, RadialProfileConsumer
+    from .pipeline import DarkStatsConsumer, PeakFinderConsumer, ProducerPipeline, RadialProfileConsumer
     from .queue.endpoint import EndOfStream, QueueEndpoint
     from .queue.ring import FrameRing, physical_slots
     from .queue.session import QueueSession
@@ -242,6 +272,12 @@ def main(argv=None) -> int:
     if args.consumer_task == "radial" and (mode == Mode.raw or int(args.panel_shards) > 1):
         log.error("--consumer_task radial needs whole calibrated frames (not --mode raw / --panel_shards)")
         return 2
+    if args.consumer_task == "dark" and (mode != Mode.raw or int(args.panel_shards) > 1):
+        log.error("--consumer_task dark needs whole raw frames (--mode raw, no --panel_shards)")
+        return 2
+    if args.out_dark is not None and args.consumer_task != "dark":
+        log.error("--out_dark belongs to --consumer_task dark")
+        return 2
     shards = int(args.panel_shards)
     if shards > 1:
         from .source.shard import PanelShardSource, shard_layout
@@ -262,6 +298,8 @@ def main(argv=None) -> int:
         if getattr(source, "calibrated", False):
             log.error("--panel_shards needs raw frames (a psana-calibrated source cannot be split into panel shards)")
             return 2
+        if args.constants is not None and not apply_constants_file(args, source, rank):
+            return 2
         source = PanelShardSource(source, shard, shards)
         log.info("Rank %d: panel shard %d/%d (panels %d:%d) of event group %d/%d", rank, shard, shards, source.lo,
                  source.hi, group, n_groups)
@@ -278,6 +316,8 @@ def main(argv=None) -> int:
             return 2
         if args.calibrate_on_read and getattr(source, "calibrated", False):
             log.error("--calibrate_on_read needs raw frames; this psana_wrapper source provides calibrated ones")
+            return 2
+        if args.constants is not None and not apply_constants_file(args, source, rank):
             return 2
     if args.start_event:
         if not hasattr(source, "seek"):
@@ -360,6 +400,8 @@ def main(argv=None) -> int:
 
                 geo = getattr(source, "geometry", None) or make_geometry(source.consts.spec)
                 cons = RadialProfileConsumer(ep, RadialBinning.from_geometry(geo, mode, 512))
+            elif args.consumer_task == "dark":
+                cons = DarkStatsConsumer(ep, source.consts.spec)
             else:
                 cons = PeakFinderConsumer(ep, frame_shape, PeakFinderParams())
             registry.register("consumer", cons.metrics)
@@ -372,6 +414,8 @@ def main(argv=None) -> int:
                         break
                 if args.consumer_task == "radial":
                     stats["radial"] = cons.synchronize()
+                elif args.consumer_task == "dark":
+                    stats["dark"] = cons.stats()
                 else:
                     stats["peaks"] = cons.synchronize()
                 stats["consumed"] = cons.frames
@@ -405,6 +449,17 @@ def main(argv=None) -> int:
                     _, run_count, run_frames = stats.get("radial", (None, np.zeros(1, np.int64), 0))
                     log.info("Rank %d: co-located consumer processed %d frames, radial accumulator of %d frames, "
                              "%d pixels", rank, stats.get("consumed", 0), run_frames, int(run_count.sum()))
+                elif args.consumer_task == "dark":
+                    ds = stats.get("dark")
+                    log.info("Rank %d: co-located consumer processed %d frames, dark statistics of %d frames, "
+                             "%d samples", rank, stats.get("consumed", 0), 0 if ds is None else ds.frames,
+                             0 if ds is None else int(ds.cnt.sum()))
+                    if ds is not None and args.out_dark:
+                        # one file per rank (they merge exactly: python -m psana_ray_amd.dark merge)
+                        root, ext = os.path.splitext(args.out_dark)
+                        path = args.out_dark if size == 1 else f"{root}.r{rank}{ext}"
+                        ds.save(path)
+                        log.info("Rank %d: dark statistics written to %s", rank, path)
                 else:
                     log.info("Rank %d: co-located consumer processed %d frames, %d peaks", rank,
                              stats.get("consumed", 0), stats.get("peaks", 0))

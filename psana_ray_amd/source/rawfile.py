@@ -25,6 +25,7 @@ from .synthetic import RawEvent, generate_raw
 log = logging.getLogger(__name__)
 
 HEADER_BYTES = 4096
+DARK_RUN_KW = {"spots": (0, 0), "bkg_photons": 0.0}   # generate_raw keywords of a dark run (mkrun --dark)
 RECORD_HEADER = 32
 
 
@@ -50,14 +51,17 @@ def write_run(path, spec: DetectorSpec, frames: np.ndarray, photon_energy: np.nd
             f.write(np.ascontiguousarray(frames[i], dtype=np.uint16).tobytes())
 
 
-def make_synthetic_run(data_dir: str, exp: str, run: int, detector: str, n_events: int, chunk: int = 16) -> Path:
-    """Materialise a synthetic run on disk (``psana-ray-mkrun``)."""
+def make_synthetic_run(data_dir: str, exp: str, run: int, detector: str, n_events: int, chunk: int = 16,
+                       dark: bool = False) -> Path:
+    """Materialise a synthetic run on disk (``psana-ray-mkrun``).  ``dark``: a run without x-rays (no
+    spots, no background photons): pedestal + common mode + noise only."""
     spec = get_detector(detector)
     consts = CalibConstants.random(spec, seed=run_seed(exp, run, spec.name))
     path = run_path(data_dir, exp, run, spec.name)
     frames_all, pe_all = [], []
     for a in range(0, n_events, chunk):
-        fr, pe = generate_raw(consts, min(chunk, n_events - a), seed=run_seed(exp, run, spec.name) + 7 + a)
+        fr, pe = generate_raw(consts, min(chunk, n_events - a), seed=run_seed(exp, run, spec.name) + 7 + a,
+                              **(DARK_RUN_KW if dark else {}))
         frames_all.append(fr)
         pe_all.append(pe)
     write_run(path, spec, np.concatenate(frames_all), np.concatenate(pe_all))

@@ -162,8 +162,10 @@ def write_xtc2_run(data_dir, exp: str, run: int, det_name: str, frames: np.ndarr
 
 
 def make_synthetic_xtc2_run(data_dir, exp: str, run: int, detector: str, n_events: int,
-                            chunk: int = 16) -> Tuple[Path, Path]:
-    """Materialise a synthetic run as XTC2-style files (``psana-ray-mkrun --format xtc2``)."""
+                            chunk: int = 16, dark: bool = False) -> Tuple[Path, Path]:
+    """Materialise a synthetic run as XTC2-style files (``psana-ray-mkrun --format xtc2``).  ``dark``: a
+    run without x-rays (no spots, no background photons)."""
+    from .rawfile import DARK_RUN_KW
     from .synthetic import generate_raw
 
     spec = get_detector(detector)
@@ -171,7 +173,8 @@ def make_synthetic_xtc2_run(data_dir, exp: str, run: int, detector: str, n_event
     big, smd = xtc2_paths(data_dir, exp, run)
     with Xtc2Writer(big, smd, spec.name, spec.kind, ndim=len(spec.frame_shape)) as w:
         for a in range(0, n_events, chunk):
-            fr, pe = generate_raw(consts, min(chunk, n_events - a), seed=run_seed(exp, run, spec.name) + 7 + a)
+            fr, pe = generate_raw(consts, min(chunk, n_events - a), seed=run_seed(exp, run, spec.name) + 7 + a,
+                                  **(DARK_RUN_KW if dark else {}))
             for i in range(fr.shape[0]):
                 w.add_event(fr[i], float(pe[i]))
     return big, smd
