@@ -214,6 +214,79 @@ def main(argv=None):
                {"rounds_us_per_frame": [round(t[0] * 1e6 / FR, 3) for t in t_dark],
                 "candidate_rmw_fraction": [round(h, 4) for h in hit],
                 "vs_calib_basic": round(md[0] / mc[0], 3)}, frames=FR)
+    if want("sparsify"):
+        # K-10 zero suppression: 64 SEPARATELY allocated calib frames; the read floor and the radial
+        # profile on the SAME frames in the same process -- alternating rounds, the median round of
+        # each.  Three thresholds (quantiles of the batch: about 0.02 %, 1 % and 5 % kept), the
+        # measured densities reported.  The pack kernel's share is measured directly: the pack phase
+        # alone, replayed on the scratch block the full launch just filled.
+        from psana_ray_amd.models import RadialBinning, make_geometry
+
+        FR, rounds, nb = 64, 5, 1024
+        C = _ext.load()
+        sraw = [pool[i % pool.shape[0]].to(dev).clone() for i in range(FR)]
+        sfl = [torch.empty(spec.frame_shape, dtype=torch.float32, device=dev) for _ in range(FR)]
+        cal.run(sraw, sfl)
+        torch.cuda.synchronize()
+        sample = torch.cat([t.reshape(-1)[::16] for t in sfl]).float()
+        sample = sample[torch.isfinite(sample)].sort().values
+        thrs = [float(sample[min(sample.numel() - 1, int(sample.numel() * (1.0 - q)))]) for q in (0.0002, 0.01, 0.05)]
+        cap = npix // 16
+        nnz = torch.zeros(FR, dtype=torch.int32, device=dev)
+        flg = torch.zeros(FR, dtype=torch.uint8, device=dev)
+        offs = torch.zeros(FR + 1, dtype=torch.int64, device=dev)
+        spix = torch.empty(FR * cap, dtype=torch.int32, device=dev)
+        sval = torch.empty(FR * cap, dtype=torch.float32, device=dev)
+        scr = torch.empty(kernels.sparsify_scratch_bytes(npix, cap, FR), dtype=torch.uint8, device=dev)
+        rb = RadialBinning.from_geometry(make_geometry(spec), "calib", nb)
+        bins = rb.bins_tensor(dev)
+        rsum = torch.zeros((FR, nb), dtype=torch.int64, device=dev)
+        rcnt = torch.zeros((FR, nb), dtype=torch.int32, device=dev)
+        rprof = torch.zeros((FR, nb), dtype=torch.float32, device=dev)
+        run = torch.zeros(2 * nb + 1, dtype=torch.int64, device=dev)
+        sums = torch.zeros(FR, dtype=torch.float32, device=dev)
+        fp64 = [int(t.data_ptr()) for t in sfl]
+
+        def sp(thr):
+            return lambda: kernels.sparsify(sfl, thr, 2.0 ** 20, cap, nnz, flg, offs, spix, sval, scratch=scr)
+
+        # every frame skipped (keys below key_min): the clear, an empty scan and the pack's header
+        # work -- what the two launches cost apart from reading and compacting frames
+        skip_keys = torch.zeros(FR, dtype=torch.int32, device=dev)
+        t_read, t_rad, t_sp, t_idle = [], [], [[] for _ in thrs], []
+        for _ in range(rounds):
+            t_read.append(timeit(lambda: C.read_f32(fp64, npix, 16, False, int(sums.data_ptr()), _ext.stream_handle()),
+                                 a.iters))
+            t_rad.append(timeit(lambda: kernels.radial_profile(sfl, bins, nb, rsum, rcnt, rprof, -2.0 ** 20, 2.0 ** 20, 8,
+                                                               run=run), a.iters))
+            for k, thr in enumerate(thrs):
+                t_sp[k].append(timeit(sp(thr), a.iters))
+            t_idle.append(timeit(lambda: kernels.sparsify(sfl, thrs[0], 2.0 ** 20, cap, nnz, flg, offs, spix, sval,
+                                                          keys=skip_keys, key_min=1, scratch=scr), a.iters))
+        med = lambda ts: sorted(ts)[rounds // 2]   # noqa: E731
+        us = lambda ts: [round(t[0] * 1e6 / FR, 3) for t in ts]   # noqa: E731
+        mr, mrad = med(t_read), med(t_rad)
+        report("read_f32 reference (K=16)", mr, FR * npix * 4, {"rounds_us_per_frame": us(t_read)}, frames=FR)
+        report("radial", mrad, FR * npix * 4 + npix * 2,
+               {"nbins": nb, "rounds_us_per_frame": us(t_rad), "vs_read_floor": round(mrad[0] / mr[0], 3)}, frames=FR)
+        report("sparsify(all frames skipped)", med(t_idle), 0, {"rounds_us_per_frame": us(t_idle)}, frames=FR)
+        for k, thr in enumerate(thrs):
+            sp(thr)()
+            torch.cuda.synchronize()
+            kept = int(nnz.sum())
+            stored = int(offs[FR])
+            ms = med(t_sp[k])
+            t_pack = timeit(lambda: C.sparsify(fp64, npix, thr, 2.0 ** 20, cap, 0, 0, 0, int(nnz.data_ptr()),
+                                               int(flg.data_ptr()), int(offs.data_ptr()), int(spix.data_ptr()),
+                                               int(sval.data_ptr()), int(scr.data_ptr()), scr.numel(),
+                                               _ext.stream_handle(), 2), a.iters)
+            report("sparsify", ms, FR * npix * 4 + stored * 16,
+                   {"thr": round(thr, 3), "cap": cap, "density": round(kept / (FR * npix), 6),
+                    "frames_overflowed": int((flg & 1).sum()), "pixels_stored": stored,
+                    "bytes_written": stored * 16 + FR * 13 + 8,   # staging + packed pairs, and the header
+                    "pack_us_per_frame": round(t_pack[0] * 1e6 / FR, 3), "pack_share": round(t_pack[0] / ms[0], 3),
+                    "rounds_us_per_frame": us(t_sp[k]), "vs_read_floor": round(ms[0] / mr[0], 3),
+                    "vs_radial": round(ms[0] / mrad[0], 3)}, frames=FR)
     if want("h2d"):
         C = _ext.load()
         hp = src.pool

@@ -378,6 +378,37 @@ PYBIND11_MODULE(_C, m) {
         py::arg("adu_hi"), py::arg("cnt"), py::arg("sum"), py::arg("sq"), py::arg("stream"),
         py::call_guard<py::gil_scoped_release>());
 
+  m.def("sparsify",
+        [](const std::vector<uint64_t>& in, int64_t n, float thr, float vmax, int64_t cap, uint64_t mask,
+           uint64_t keys, int key_min, uint64_t nnz, uint64_t flags, uint64_t offs, uint64_t pix, uint64_t val,
+           uint64_t scratch, int64_t scratch_bytes, uint64_t stream, int phases) {
+          pr::launch_sparsify(make_ptrs(in, in), (int)in.size(), n, thr, vmax, cap, mask, keys, key_min, nnz, flags,
+                              offs, pix, val, scratch, scratch_bytes, stream, phases);
+        },
+        py::arg("in_ptrs"), py::arg("n"), py::arg("thr"), py::arg("vmax"), py::arg("cap"), py::arg("mask"),
+        py::arg("keys"), py::arg("key_min"), py::arg("nnz"), py::arg("flags"), py::arg("offs"), py::arg("pix"),
+        py::arg("val"), py::arg("scratch"), py::arg("scratch_bytes"), py::arg("stream"), py::arg("phases") = 3,
+        "K-10 zero suppression of up to 64 frames: nnz / flags / offs and the packed (pix, val) pairs");
+  m.attr("SPARSE_CHUNK") = pr::kSparseChunk;
+  m.def("sparsify_scratch_bytes", &pr::sparsify_scratch_bytes, py::arg("n"), py::arg("cap"), py::arg("frames"));
+  // consumer hot path: ring slots -> sparse batch (clear, scan, pack), one native call
+  m.def("sparsify_slots",
+        [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int64_t n, float thr,
+           float vmax, int64_t cap, uint64_t mask, uint64_t keys, int key_min, uint64_t nnz, uint64_t flags,
+           uint64_t offs, uint64_t pix, uint64_t val, uint64_t scratch, int64_t scratch_bytes, uint64_t stream) {
+          const int ns = (int)slots.size();
+          pr::check(ns >= 1 && ns <= pr::kMaxFrames, "sparsify_slots: 1..64 slots per batch");
+          pr::check(slot_bytes >= n * 4, "sparsify_slots: frame larger than a slot");
+          std::vector<uint64_t> in(ns);
+          for (int i = 0; i < ns; ++i) in[i] = pool.slot_ptr(slots[i]);
+          pr::launch_sparsify(make_ptrs(in, in), ns, n, thr, vmax, cap, mask, keys, key_min, nnz, flags, offs, pix,
+                              val, scratch, scratch_bytes, stream);
+        },
+        py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("n"), py::arg("thr"), py::arg("vmax"),
+        py::arg("cap"), py::arg("mask"), py::arg("keys"), py::arg("key_min"), py::arg("nnz"), py::arg("flags"),
+        py::arg("offs"), py::arg("pix"), py::arg("val"), py::arg("scratch"), py::arg("scratch_bytes"),
+        py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+
   m.def("copy_h2d_kernel",
         [](uint64_t dst, uint64_t src, int64_t bytes, int workgroups, uint64_t stream) {
           return pr::launch_copy_h2d(dst, src, bytes, workgroups, stream);

@@ -74,4 +74,17 @@ void launch_radial(const FramePtrs& fp, int nframes, int64_t n, uint64_t bins, i
 // two launches in flight must not share accumulators.
 void launch_dark(const FramePtrs& fp, int nframes, int64_t n, int kind, int adu_lo, int adu_hi, uint64_t cnt,
                  uint64_t sum, uint64_t sq, uint64_t stream);
+// K-10 zero suppression (csrc/sparse.hip): the pixels of up to kMaxFrames float32 frames of n elements
+// with thr <= v <= vmax (and mask[i] != 0 when mask != 0), as (index, value) pairs packed frame after
+// frame in index order.  nnz int32 [F], flags uint8 [F] (bit 0 overflow, bit 1 skipped), offs int64
+// [F + 1], pix int32 / val float32 [>= F * cap].  keys (int32 [F] on the device, or 0): frame f is
+// skipped unless keys[f] >= key_min.  scratch: a 16-B aligned block of at least
+// sparsify_scratch_bytes(n, cap, F) bytes, owned by one stream; the launch clears what it needs.
+constexpr int kSparseChunk = 4096;          // elements per scan chunk (one directory entry each)
+constexpr int kSparseScratchHeader = 256;   // the frames' cursors
+int64_t sparsify_scratch_bytes(int64_t n, int64_t cap, int frames);
+void launch_sparsify(const FramePtrs& fp, int nframes, int64_t n, float thr, float vmax, int64_t cap, uint64_t mask,
+                     uint64_t keys, int key_min, uint64_t nnz, uint64_t flags, uint64_t offs, uint64_t pix,
+                     uint64_t val, uint64_t scratch, int64_t scratch_bytes, uint64_t stream,
+                     int phases = 3);   // measurements only: 1 = clear + scan, 2 = pack of a block just scanned
 }  // namespace pr

@@ -9,9 +9,12 @@ example's 3-field unpack, Q-1) until the explicit end of stream (fixing Q-2), an
 ``print`` (the reference example's behaviour), ``peakfind`` (on-GPU K-07 peak finder over
 zero-copy leased batches), ``radial`` (on-GPU K-08 azimuthal integration: per-frame radial profiles
 and an exact integer run accumulator), ``dark`` (on-GPU K-09 dark-run statistics of a RAW queue:
-per-pixel integer count / sum / sum of squares per gain candidate) or ``none``.  ``--out`` writes the
-peak lists / the radial accumulator / the dark statistics to an ``.npz`` (several consumers' radial
-files add with ``psana_ray_amd.radial.merge``, dark files with ``psana_ray_amd.dark.merge``).
+per-pixel integer count / sum / sum of squares per gain candidate), ``sparse`` (on-GPU K-10 zero
+suppression: the pixels inside a value window as (index, value) pairs, optionally only of frames with
+at least ``--min_peaks`` peaks) or ``none``.  ``--out`` writes the peak lists / the radial accumulator /
+the dark statistics / the sparse frames to an ``.npz`` (several consumers' radial files add with
+``psana_ray_amd.radial.merge``, dark files with ``psana_ray_amd.dark.merge``, sparse files join with
+``psana_ray_amd.sparse.merge``).
 """
 from __future__ import annotations
 
@@ -36,10 +39,11 @@ def build_parser():
     ap.add_argument("--ray_namespace", type=str, default=DEFAULT_RAY_NAMESPACE)
     ap.add_argument("--queue_name", type=str, default=DEFAULT_QUEUE_NAME)
     ap.add_argument("--device", type=str, default=None)
-    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "train", "none"],
+    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "train", "none"],
                     help="train: online PeakNetLite training from peak-finder labels (trainer.py); radial: radial "
                          "profile I(r) / I(q) of every frame + run accumulator (--nbins ... --radial_mask); dark: "
-                         "per-pixel dark-run statistics of a RAW queue (--adu_min / --adu_max)")
+                         "per-pixel dark-run statistics of a RAW queue (--adu_min / --adu_max); sparse: zero-suppressed "
+                         "frames to disk (--sparse_thr ... --min_peaks)")
     ap.add_argument("--lr", type=float, default=1e-3, help="--task train: AdamW learning rate")
     ap.add_argument("--save", type=str, default=None, help="--task train: write the model state_dict here")
     ap.add_argument("--ddp", action="store_true",
@@ -56,7 +60,8 @@ def build_parser():
     ap.add_argument("--son_min", type=float, default=5.0)
     ap.add_argument("--out", type=str, default=None,
                     help="write peaks (npz) when --task peakfind; the radial accumulator + per-frame profiles (npz) "
-                         "when --task radial; the dark statistics (psana_ray_amd.dark.DarkStats npz) when --task dark")
+                         "when --task radial; the dark statistics (psana_ray_amd.dark.DarkStats npz) when --task dark; "
+                         "the sparse frames (psana_ray_amd.sparse.SparseFrames npz) when --task sparse")
     g = ap.add_argument_group("--task radial")
     g.add_argument("--nbins", type=int, default=512, help="radial bins (1 .. 4096)")
     g.add_argument("--center", type=str, default=None, help="beam centre Y,X in image pixels (default: image centre)")
@@ -74,11 +79,30 @@ def build_parser():
     g = ap.add_argument_group("--task dark")
     g.add_argument("--adu_min", type=int, default=0, help="ADU window: samples below are ignored (default 0)")
     g.add_argument("--adu_max", type=int, default=65535, help="ADU window: samples above are ignored (default 65535)")
+    add_sparse_arguments(ap)
     ap.add_argument("--timeout", type=float, default=300.0)
     ap.add_argument("--metrics_interval", type=float, default=10.0, help="seconds between rate lines; 0 disables")
     ap.add_argument("--metrics_json", type=str, default=None, help="append per-interval metrics as JSON lines")
     ap.add_argument("--log_level", type=str, default=DEFAULT_LOG_LEVEL, choices=LOG_LEVELS)
     return ap
+
+
+def add_sparse_arguments(ap):
+    """The flags of ``--task sparse`` (the producer CLI's ``--consumer_task sparse`` takes the same)."""
+    g = ap.add_argument_group("--task sparse")
+    g.add_argument("--sparse_thr", type=float, default=20.0,
+                   help="keep pixels with thr <= value (default 20.0, the peak finder's threshold)")
+    g.add_argument("--sparse_vmax", type=float, default=float(2 ** 20), help="... and value <= vmax (default 2^20)")
+    g.add_argument("--sparse_cap", type=int, default=None,
+                   help="pixels kept per frame at most (default n // 16); a frame with more stores nothing and is "
+                        "flagged")
+    g.add_argument("--sparse_mask", type=str, default=None, help="frame-shaped uint8 .npy, 1 = keep")
+    g.add_argument("--min_peaks", type=int, default=0,
+                   help="hit filter: keep a frame only if the peak finder (--thr_peak / --son_min) finds at least N "
+                        "peaks, decided on the device (default 0: no peak finder)")
+    g.add_argument("--part_frames", type=int, default=0,
+                   help="K > 0: write parts STEM.00000.npz, ... of at most K frames while running, instead of one "
+                        "file at the end")
 
 
 def _init_data_parallel(device) -> int:
@@ -260,6 +284,181 @@ def run_dark(args, reader, stop, progress) -> int:
     return rc
 
 
+class SparseWriter:
+    """Where the finished batches of --task sparse go.  ``part_frames == 0``: everything is kept and
+    written to ``out`` by :meth:`close`.  ``part_frames = K > 0``: parts ``stem.00000.npz, ...`` of at
+    most K frames, written by ONE background thread through a queue of depth 1 -- the run holds at
+    most two parts in host memory (the one being filled and the one being written)."""
+
+    def __init__(self, out, part_frames: int = 0):
+        import queue
+        import threading
+
+        self.out = out
+        self.part_frames = max(0, int(part_frames or 0))
+        self.paths = []
+        self._held, self._held_frames, self._part = [], 0, 0
+        self._error = None
+        self._q = self._thread = None
+        if out and self.part_frames:
+            self._q = queue.Queue(maxsize=1)
+            self._thread = threading.Thread(target=self._work, name="sparse-writer", daemon=True)
+            self._thread.start()
+
+    def part_path(self, k: int) -> str:
+        stem = self.out[:-4] if self.out.endswith(".npz") else self.out
+        return f"{stem}.{k:05d}.npz"
+
+    def _work(self):
+        from . import sparse
+
+        while True:
+            job = self._q.get()
+            if job is None:
+                return
+            path, parts = job
+            try:
+                sparse.concat(parts).save(path)
+            except Exception as e:  # noqa: BLE001 - reported by close()
+                self._error = e
+
+    def _emit(self, parts):
+        path = self.part_path(self._part)
+        self._part += 1
+        self.paths.append(path)
+        self._q.put((path, parts))   # blocks while the previous part is still being written
+
+    def add(self, batches):
+        """Finished batches (SparseFrames), oldest first."""
+        if not self.out:
+            return
+        for sf in batches:
+            if not self.part_frames:
+                self._held.append(sf)
+                continue
+            a = 0
+            while a < len(sf):   # cut the batch at part boundaries
+                take = min(len(sf) - a, self.part_frames - self._held_frames)
+                self._held.append(sf if take == len(sf) else sf.select(range(a, a + take)))
+                self._held_frames += take
+                a += take
+                if self._held_frames == self.part_frames:
+                    self._emit(self._held)
+                    self._held, self._held_frames = [], 0
+
+    def close(self, empty):
+        """Write what is left.  ``empty``: a SparseFrames of no frames with the run's parameters (a run
+        without frames still writes its file)."""
+        from . import sparse
+
+        if not self.out:
+            return
+        if self.part_frames:
+            if self._held or not self.paths:
+                self._emit(self._held or [empty])
+            self._q.put(None)
+            self._thread.join()
+            if self._error is not None:
+                raise self._error
+        else:
+            sparse.concat(self._held or [empty]).save(self.out)
+            self.paths.append(self.out)
+
+
+def load_sparse_mask(path, shape):
+    """``--sparse_mask``: a uint8 keep-mask [n] of the frames' shape (an image may come without its
+    leading axis of 1), or None; ValueError for another shape."""
+    import numpy as np
+
+    if not path:
+        return None
+    mask = np.load(path)   # allow_pickle stays False
+    shape = tuple(shape)
+    if tuple(mask.shape) != shape and not (shape[0] == 1 and tuple(mask.shape) == shape[1:]):
+        raise ValueError(f"--sparse_mask is {tuple(mask.shape)}, the frames are {shape}")
+    return (mask != 0).astype(np.uint8).reshape(-1)
+
+
+def sparse_layout(reader, args):
+    """(detector name, layout, frame shape) of the frames --task sparse will see, or a ValueError."""
+    import torch
+
+    det = (reader.session_meta or {}).get("detector") or {}
+    name = det.get("name") or getattr(args, "detector_name", None) or ""
+    ring = reader.endpoint.ring
+    cal = reader.calibrator
+    if cal is not None:
+        return name, cal.mode.value, tuple(cal.out_shape)
+    shape = tuple(ring.frame_shape)
+    layout = det.get("mode")
+    if ring.dtype != torch.float32 or layout == "raw":
+        raise ValueError("the queue carries raw uint16 frames without a calibration recipe; zero suppression needs "
+                         "calibrated ones (a producer with --mode calib / image, or --calibrate_on_read)")
+    if layout is None:
+        layout = "calib" if len(shape) == 3 else "image"
+    return name, layout, shape
+
+
+def run_sparse(args, reader, stop, progress) -> int:
+    """--task sparse: zero-suppress until the end of the stream; ``progress["n"]`` counts frames."""
+    from .config import PeakFinderParams
+    from .data_reader import DataReaderError, EndOfStream
+    from .pipeline import SparseFrameConsumer
+    from .queue.endpoint import EndOfStream as QueueEOS
+    from .queue.endpoint import QueuePeerError
+
+    cid = reader.consumer_id
+    if reader.endpoint is None:
+        log.error("--task sparse needs the distributed queue (a producer session)")
+        return 2
+    if reader.panel_shards > 1:
+        log.error("--task sparse: the producers queue panel shards (--panel_shards %d); sparse frames need whole "
+                  "frames (out of scope)", reader.panel_shards)
+        return 2
+    cal = reader.calibrator
+    try:
+        name, layout, shape = sparse_layout(reader, args)
+        mask = load_sparse_mask(args.sparse_mask, shape)
+        cons = SparseFrameConsumer(reader.endpoint, shape, thr=args.sparse_thr, vmax=args.sparse_vmax,
+                                   cap=args.sparse_cap, mask=mask, min_peaks=args.min_peaks,
+                                   peak_params=PeakFinderParams(thr_peak=args.thr_peak, son_min=args.son_min),
+                                   detector=name, layout=layout, batch=args.batch, check_ring=cal is None)
+    except (ValueError, KeyError, OSError) as e:
+        log.error("--task sparse: %s", e)
+        return 2
+    writer = SparseWriter(args.out, args.part_frames)
+    rc = 0
+    try:
+        while not stop["flag"] and (args.max_frames is None or progress["n"] < args.max_frames):
+            left = None if args.max_frames is None else args.max_frames - progress["n"]
+            if cal is None:
+                cons.poll(timeout=1.0, max_items=left)
+            else:   # raw ring (--calibrate_on_read): calibrate here, then sparsify
+                items = reader.read_batch(cons.batch if left is None else min(cons.batch, left), timeout=1.0)
+                if items:
+                    meta = [(it.rank, it.idx, it.gevt, it.photon_energy) for it in items]
+                    frames = reader.calibrate(items)
+                    st = cons.process_frames([frames[i] for i in range(len(items))], meta)
+                    if st is not None:
+                        frames.record_stream(st)
+            progress["n"] = cons.frames
+            writer.add(cons.take_results())
+    except (EndOfStream, QueueEOS):
+        log.info("Consumer %s: end of stream", cid)
+    except (DataReaderError, QueuePeerError) as e:
+        print(f"DataReader error: {e}")
+        print("Queue actor is dead. Exiting...")
+        rc = 1
+    progress["n"] = cons.frames
+    cons.synchronize()
+    writer.add(cons.take_results())
+    writer.close(cons.empty())
+    m = cons.metrics()
+    print(f"Consumer {cid} sparse: frames={cons.frames} stored={m['frames_stored']} skipped={m['frames_skipped']} "
+          f"overflowed={m['frames_overflowed']} pixels={m['pixels_stored']}", flush=True)
+    return rc
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=getattr(logging, args.log_level), format="%(asctime)s - %(levelname)s - %(message)s")
@@ -312,6 +511,14 @@ def main(argv=None) -> int:
             if rc:
                 reporter.stop(final_sample=False)
                 return rc
+        if args.task == "sparse":
+            progress = {"n": 0}
+            registry.register("sparse", lambda: {"frames_consumed": progress["n"]})
+            rc = run_sparse(args, reader, stop, progress)
+            n = progress["n"]
+            if rc:
+                reporter.stop(final_sample=False)
+                return rc
         if args.task == "peakfind":
             from .ops import kernels
 
@@ -351,7 +558,7 @@ def main(argv=None) -> int:
                 import torch.distributed as dist
 
                 dist.destroy_process_group()
-        while args.task not in ("train", "radial", "dark") and not stop["flag"] and (args.max_frames is None or n < args.max_frames):
+        while args.task not in ("train", "radial", "dark", "sparse") and not stop["flag"] and (args.max_frames is None or n < args.max_frames):
             try:
                 if args.task == "peakfind" and reader.endpoint is not None:
                     items = reader.read_batch(args.batch, timeout=1.0)

@@ -1,4 +1,4 @@
-"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-09).
+"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-10).
 
 Every wrapper checks device / dtype / shape / contiguity / alignment on the host BEFORE the
 launch (a mis-shaped launch of a hand-written kernel can fault the GPU), splits batches into
@@ -286,6 +286,87 @@ def dark_accumulate(frames: Sequence[torch.Tensor], kind: int, adu_lo: int, adu_
     s = _ext.stream_handle(stream)
     for a, b in _chunks(F):
         C.dark([_ptr(t) for t in frames[a:b]], n, kind, adu_lo, adu_hi, _ptr(cnt), _ptr(sum), _ptr(sq), s)
+
+
+# elements per chunk of the K-10 scan (csrc/kernels.h kSparseChunk): one directory entry per chunk
+SPARSE_CHUNK = 4096
+
+
+def sparsify_scratch_bytes(n: int, cap: int, frames: int) -> int:
+    """Bytes of the K-10 scratch block (cursors, chunk directory, staging rows) for batches of up to
+    ``frames`` frames of ``n`` elements at ``cap`` entries per frame.  Pure arithmetic (the extension's
+    sparsify_scratch_bytes computes the same figure; the launcher checks the block against its own)."""
+    n, cap, frames = int(n), int(cap), int(frames)
+    if not 1 <= n < 2 ** 31 or not 1 <= frames <= MAX_FRAMES or cap < 1 or frames * cap >= 2 ** 31:
+        raise ValueError("sparsify_scratch_bytes: n, cap or frames out of range")
+    chunks = max(1, (n // 4 + SPARSE_CHUNK // 4 - 1) // (SPARSE_CHUNK // 4))
+    return 256 + (chunks * frames * 8 + 15) // 16 * 16 + frames * cap * 8
+
+
+def sparsify(frames: Sequence[torch.Tensor], thr: float, vmax: float, cap: int, nnz: torch.Tensor,
+             flags: torch.Tensor, offs: torch.Tensor, pix: torch.Tensor, val: torch.Tensor,
+             mask: Optional[torch.Tensor] = None, keys: Optional[torch.Tensor] = None, key_min: int = 0,
+             scratch: Optional[torch.Tensor] = None, stream=None):
+    """K-10 zero suppression (csrc/sparse.hip; contract: ops.reference.sparsify_reference).
+    frames: F (1 .. 64) float32 tensors of n elements (any layout) on one GPU.  Outputs (overwritten, no
+    clearing needed): nnz int32 [F], flags uint8 [F] (bit 0 overflow, bit 1 skipped), offs int64
+    [F + 1], pix int32 / val float32 of at least F * cap elements -- frame f's kept pixels at
+    offs[f] .. offs[f + 1]; elements from offs[F] on are unspecified.  ``mask``: uint8 [n], non-zero =
+    keep.  ``keys``: int32 [F] on the device; frame f is skipped unless keys[f] >= key_min.
+    ``scratch``: a contiguous, 16-B aligned tensor of at least sparsify_scratch_bytes(n, cap, F) bytes
+    that no other launch in flight uses (allocated here when None).  Everything is checked here,
+    before any launch."""
+    from .reference import validate_sparse_params
+
+    F = len(frames)
+    if not 1 <= F <= MAX_FRAMES:
+        raise ValueError(f"sparsify: 1 .. {MAX_FRAMES} frames per launch, got {F}")
+    thr, vmax, cap = validate_sparse_params(thr, vmax, cap, F)
+    try:
+        key_min = operator.index(key_min)
+    except TypeError:
+        raise ValueError("sparsify: key_min must be an integer") from None
+    if not -2 ** 31 <= key_min < 2 ** 31:
+        raise ValueError("sparsify: key_min must fit an int32")
+    if not isinstance(frames[0], torch.Tensor):
+        raise ValueError("sparsify: frames must be tensors")
+    dev = frames[0].device
+    n = frames[0].numel()
+    if dev.type != "cuda":
+        raise ValueError(f"sparsify: frames on {dev}, expected a GPU")
+    if not 1 <= n < 2 ** 31:
+        raise ValueError("sparsify: frames must have 1 .. 2^31 - 1 elements")
+    _check_frames(frames, torch.float32, n, dev, "sparsify in")
+    for t, dt, k, name in ((nnz, torch.int32, F, "nnz"), (flags, torch.uint8, F, "flags"),
+                           (offs, torch.int64, F + 1, "offs")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.shape != (k,) or t.device != dev \
+                or not t.is_contiguous():
+            raise ValueError(f"sparsify: {name} must be a contiguous {dt} [{k}] tensor on {dev}")
+    for t, dt, name in ((pix, torch.int32, "pix"), (val, torch.float32, "val")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() < F * cap or t.device != dev \
+                or not t.is_contiguous():
+            raise ValueError(f"sparsify: {name} must be a contiguous {dt} tensor of at least F * cap = {F * cap} "
+                             f"elements on {dev}")
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.numel() != n
+                             or mask.device != dev or not mask.is_contiguous() or _ptr(mask) % 4):
+        raise ValueError(f"sparsify: mask must be a contiguous, 4-B aligned uint8 [{n}] tensor on {dev}")
+    if keys is not None and (not isinstance(keys, torch.Tensor) or keys.dtype != torch.int32 or keys.numel() != F
+                             or keys.device != dev or not keys.is_contiguous()):
+        raise ValueError(f"sparsify: keys must be a contiguous int32 [{F}] tensor on {dev}")
+    need = sparsify_scratch_bytes(n, cap, F)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not isinstance(scratch, torch.Tensor) or scratch.device != dev or not scratch.is_contiguous() \
+            or _ptr(scratch) % 16 or scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"sparsify: scratch must be a contiguous, 16-B aligned tensor of at least {need} bytes "
+                         f"on {dev} (sparsify_scratch_bytes)")
+    C = _ext.load()
+    if C.SPARSE_CHUNK != SPARSE_CHUNK or C.sparsify_scratch_bytes(n, cap, F) != need:
+        raise RuntimeError("sparsify: SPARSE_CHUNK / sparsify_scratch_bytes disagree with the extension")
+    s = _ext.stream_handle(stream)
+    C.sparsify([_ptr(t) for t in frames], n, thr, vmax, cap, 0 if mask is None else _ptr(mask),
+               0 if keys is None else _ptr(keys), key_min, _ptr(nnz), _ptr(flags), _ptr(offs), _ptr(pix), _ptr(val),
+               _ptr(scratch), scratch.numel() * scratch.element_size(), s)
 
 
 def mask_frames(frames: Sequence[torch.Tensor], zero: torch.Tensor, stream=None):

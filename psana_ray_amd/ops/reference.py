@@ -8,6 +8,7 @@ caught too.
 """
 from __future__ import annotations
 
+import operator
 from typing import List, Optional
 
 import numpy as np
@@ -277,3 +278,80 @@ def dark_accumulate_reference(frames: torch.Tensor, kind: int, adu_lo: int, adu_
         s.append((m * adu).sum(dim=0))
         q.append((m * adu * adu).sum(dim=0))
     return torch.stack(cnt).to(torch.int32), torch.stack(s), torch.stack(q)
+
+
+SPARSE_MAX_FRAMES = 64
+SPARSE_FLAG_OVERFLOW = 1   # nnz[f] > cap: the frame stores nothing
+SPARSE_FLAG_SKIPPED = 2    # keys[f] < key_min: the frame was not looked at
+
+
+def validate_sparse_params(thr, vmax, cap, frames: int, what: str = "sparsify"):
+    """(thr, vmax) as the float32 values the kernel sees and cap as a Python int, or ValueError."""
+    try:
+        cap = operator.index(cap)
+    except TypeError:
+        raise ValueError(f"{what}: cap must be an integer, got {cap!r}") from None
+    with np.errstate(over="ignore"):   # a double beyond the float32 range becomes inf and is refused
+        lo, hi = float(np.float32(thr)), float(np.float32(vmax))
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"{what}: the value window must be finite, got [{thr}, {vmax}]")
+    if not lo <= hi:
+        raise ValueError(f"{what}: empty value window [{thr}, {vmax}]")
+    if cap < 1 or int(frames) * cap >= 2 ** 31:
+        raise ValueError(f"{what}: cap must be >= 1 with F * cap < 2^31, got cap {cap} for {frames} frames")
+    return lo, hi, cap
+
+
+def sparsify_reference(frames: torch.Tensor, thr: float, vmax: float, cap: int, mask=None, keys=None,
+                       key_min: int = 0):
+    """K-10 golden: zero suppression.  ``frames``: [F, ...] float32 (any frame layout of n elements),
+    1 <= F <= 64.  A pixel is kept iff its ``mask`` entry (uint8 [n], when given) is non-zero and
+    thr <= v <= vmax (NaN fails, +-inf is outside the finite window, -0.0 is kept iff thr <= 0 with its
+    sign bit).  Frame f is processed iff ``keys`` (int32 [F]) is absent or keys[f] >= key_min;
+    otherwise it is skipped (nnz 0, flag bit 1).  Returns (nnz int32 [F] -- exact, also past cap --,
+    flags uint8 [F] -- bit 0 = nnz > cap --, offs int64 [F + 1], pix int32 [offs[F]], val float32
+    [offs[F]]): frame f's kept pixels in ascending index order at offs[f] .. offs[f + 1], none when it
+    overflows."""
+    F = int(frames.shape[0])
+    if not 1 <= F <= SPARSE_MAX_FRAMES:
+        raise ValueError(f"sparsify: 1 .. {SPARSE_MAX_FRAMES} frames per batch, got {F}")
+    if frames.dtype != torch.float32:
+        raise ValueError(f"sparsify: frames must be float32, got {frames.dtype}")
+    lo, hi, cap = validate_sparse_params(thr, vmax, cap, F)
+    x = frames.detach().cpu().reshape(F, -1)
+    n = x.shape[1]
+    if not 1 <= n < 2 ** 31:
+        raise ValueError("sparsify: frames must have 1 .. 2^31 - 1 elements")
+    keep = (x >= lo) & (x <= hi)
+    if mask is not None:
+        m = torch.as_tensor(np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask)).reshape(-1)
+        if m.dtype != torch.uint8 or m.numel() != n:
+            raise ValueError(f"sparsify: mask must be uint8 [{n}]")
+        keep &= (m != 0).unsqueeze(0)
+    live = torch.ones(F, dtype=torch.bool)
+    if keys is not None:
+        k = torch.as_tensor(np.asarray(keys.cpu() if isinstance(keys, torch.Tensor) else keys)).reshape(-1)
+        if k.dtype != torch.int32 or k.numel() != F:
+            raise ValueError(f"sparsify: keys must be int32 [{F}]")
+        live = k >= int(key_min)
+    nnz = torch.zeros(F, dtype=torch.int32)
+    flags = torch.zeros(F, dtype=torch.uint8)
+    offs = torch.zeros(F + 1, dtype=torch.int64)
+    pix, val = [], []
+    for f in range(F):
+        stored = 0
+        if not bool(live[f]):
+            flags[f] = SPARSE_FLAG_SKIPPED
+        else:
+            idx = torch.nonzero(keep[f]).reshape(-1)   # ascending
+            nnz[f] = idx.numel()
+            if idx.numel() > cap:
+                flags[f] = SPARSE_FLAG_OVERFLOW
+            else:
+                stored = idx.numel()
+                pix.append(idx.to(torch.int32))
+                val.append(x[f][idx])
+        offs[f + 1] = offs[f] + stored
+    pix = torch.cat(pix) if pix else torch.zeros(0, dtype=torch.int32)
+    val = torch.cat(val) if val else torch.zeros(0, dtype=torch.float32)
+    return nnz, flags, offs, pix, val

@@ -13,7 +13,9 @@ Producer (replaces psana_ray/producer.py:78-117, ``produce_data``):
 
 Consumer: drains this rank's shard in batches and runs the on-GPU peak finder (K-07) on a
 consumer stream, releasing slots stream-ordered (BASELINE config 5); RadialProfileConsumer runs the
-radial profile (K-08) the same way and keeps an exact integer run accumulator on the device.
+radial profile (K-08) the same way and keeps an exact integer run accumulator on the device;
+SparseFrameConsumer writes the pixels above a threshold as (index, value) pairs (K-10), optionally only
+of the frames the peak finder calls hits.
 """
 from __future__ import annotations
 
@@ -945,3 +947,307 @@ class DarkStatsConsumer:
 
         cnt, s, q, frames = self.synchronize()
         return DarkStats(self.spec.name, self.kind, self.adu_lo, self.adu_hi, frames, cnt.copy(), s.copy(), q.copy())
+
+
+class SparseFrameConsumer:
+    """Consumer engine: batches of leased slots -> K-10 zero suppression (csrc/sparse.hip) ->
+    stream-ordered release.  Same surface and stream scheme as :class:`RadialProfileConsumer`.
+
+    Per frame: the (pixel index, value) pairs with ``thr <= v <= vmax`` (and ``mask != 0``), packed in
+    index order; at most ``cap`` per frame (a frame with more stores nothing and is flagged).  With
+    ``min_peaks > 0`` the peak finder (K-07) runs first on the same stream and its per-frame counts
+    decide ON THE DEVICE which frames are looked at -- no host round trip.  Results reach the host
+    through pinned buffers in two steps per batch: the header (nnz, flags, offs) first, then exactly
+    ``offs[F]`` elements of pix and val; the wait for a batch's header happens after the NEXT batch
+    (on the other stream) has been issued.  Finished batches collect in :attr:`results` as
+    :class:`psana_ray_amd.sparse.SparseFrames` (``take_results`` hands them over).  Ring slots are
+    released stream-ordered after the scan, not after the copies.  CPU endpoints run the golden
+    model (ops.reference)."""
+
+    def __init__(self, endpoint: QueueEndpoint, frame_shape, thr: Optional[float] = None, vmax: Optional[float] = None,
+                 cap: Optional[int] = None, mask=None, min_peaks: int = 0, peak_params: Optional[PeakFinderParams] = None,
+                 detector: str = "", layout: str = "calib", batch: Optional[int] = None,
+                 stream_kind: str = CONSUMER_STREAM_KIND, streams: int = CONSUMER_STREAMS,
+                 ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
+        """frame_shape: the shape of a (calibrated) frame.  check_ring=False: the queue carries RAW
+        frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
+        from . import sparse as _sparse
+        from .ops.reference import validate_sparse_params
+
+        self.ep = endpoint
+        self.shape = tuple(int(s) for s in frame_shape)
+        self.n = int(np.prod(self.shape))
+        self.batch = min(resolve_consumer_batch(batch, ranks_per_gpu), kernels.MAX_FRAMES)
+        if not 1 <= self.n < 2 ** 31:
+            raise ValueError("sparse: frames must have 1 .. 2^31 - 1 elements")
+        self.thr, self.vmax, self.cap = validate_sparse_params(
+            _sparse.DEFAULT_THR if thr is None else thr, _sparse.DEFAULT_VMAX if vmax is None else vmax,
+            _sparse.default_cap(self.n) if cap is None else cap, self.batch, "sparse")
+        self.min_peaks = int(min_peaks)
+        if self.min_peaks < 0:
+            raise ValueError("sparse: min_peaks must be >= 0")
+        self.peak_params = peak_params or PeakFinderParams()
+        if self.min_peaks > 0:
+            if len(self.shape) not in (2, 3):
+                raise ValueError(f"sparse: the hit filter needs 2-D or 3-D frames, got {self.shape}")
+            if self.peak_params.radius not in (1, 2):
+                raise ValueError("sparse: peak finder radius must be 1 or 2")
+            self._pf_shape = self.shape if len(self.shape) == 3 else (1, *self.shape)
+        self.detector, self.layout = str(detector), str(layout)
+        self.device = endpoint.ring.device
+        self.gpu = self.device.type == "cuda"
+        if check_ring:
+            if endpoint.ring.dtype != torch.float32:
+                raise ValueError(f"sparse: the queue carries {endpoint.ring.dtype} frames, zero suppression needs "
+                                 "calibrated float32 ones")
+            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
+                raise ValueError(f"sparse: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+        self._mask_np = None
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.dtype != np.uint8 or m.size != self.n or (m.ndim > 1 and tuple(m.shape) != self.shape):
+                raise ValueError(f"sparse: the mask must be uint8 of the frame's shape {self.shape}, got {m.dtype} "
+                                 f"{tuple(m.shape)}")
+            self._mask_np = np.ascontiguousarray(m.reshape(-1))
+        self.frames = 0
+        self.frames_stored = self.frames_skipped = self.frames_overflowed = self.pixels_stored = 0
+        self.results = []      # finished batches (SparseFrames), oldest first
+        self._pending = collections.deque()   # GPU batches in flight: dicts, oldest first
+        self._lock = threading.Lock()
+        if self.gpu:
+            self.streams = _make_streams(self.device, int(streams), stream_kind, owner=self)
+            self.stream = self.streams[0]
+            B, dev = self.batch, self.device
+            self._nbuf = 2 * len(self.streams)   # buffer k % nbuf is reused by launch k + nbuf, on k's stream
+            # header of a batch in ONE row: offs int64 [B + 1] | nnz int32 [B] | flags uint8 [B]
+            self._hdr_bytes = 8 * (B + 1) + 4 * B + B
+            self._hdr = torch.zeros((self._nbuf, (self._hdr_bytes + 15) // 16 * 16), dtype=torch.uint8, device=dev)
+            self._hdr_host = torch.zeros(self._hdr.shape, dtype=torch.uint8, pin_memory=True)
+            self._pix = torch.empty((self._nbuf, B * self.cap), dtype=torch.int32, device=dev)
+            self._val = torch.empty((self._nbuf, B * self.cap), dtype=torch.float32, device=dev)
+            # one scratch block per stream (a block must never serve two launches in flight)
+            self._scratch = [torch.empty(kernels.sparsify_scratch_bytes(self.n, self.cap, B), dtype=torch.uint8, device=dev)
+                             for _ in self.streams]
+            self._mask = None if self._mask_np is None else torch.from_numpy(self._mask_np).to(dev)
+            if self.min_peaks > 0:
+                p = self.peak_params
+                self._peaks = torch.empty((self._nbuf, B, p.max_peaks, 8), dtype=torch.float32, device=dev)
+                self._meta = torch.zeros((self._nbuf, 3 * B), dtype=torch.int32, device=dev)
+                self._counts = self._meta[:, :B]
+                self._summary = self._meta[:, B:].view(torch.float32).view(self._nbuf, B, 2)
+                self._pf_scratch = [torch.zeros(kernels.PF_SCRATCH_WORDS, dtype=torch.int32, device=dev)
+                                    for _ in self.streams]
+                self._pf_total = torch.zeros((), dtype=torch.int64, device=dev)
+            self._b = 0
+
+    # ------------------------------------------------------------------ buffers
+    def _views(self, b: int, n: int):
+        """(offs [n + 1], nnz [n], flags [n]) views of header row b on the device."""
+        B = self.batch
+        row = self._hdr[b]
+        return (row[:8 * (B + 1)].view(torch.int64)[:n + 1], row[8 * (B + 1):8 * (B + 1) + 4 * B].view(torch.int32)[:n],
+                row[8 * (B + 1) + 4 * B:self._hdr_bytes][:n])
+
+    def _next(self):
+        b = self._b % self._nbuf
+        k = self._b % len(self.streams)
+        self._b += 1
+        return b, k, self.streams[k]
+
+    def _sparse_frames(self, meta, nnz, flags, offs, pix, val):
+        from .sparse import SparseFrames
+
+        return SparseFrames(self.detector, self.layout, self.shape, self.thr, self.vmax, self.cap, self.min_peaks,
+                            self._peak_dict(), rank=[m[0] for m in meta], idx=[m[1] for m in meta],
+                            gevt=[m[2] for m in meta],
+                            photon_energy=[float("nan") if m[3] is None else float(m[3]) for m in meta],
+                            nnz=nnz, flags=flags, offs=offs, pix=pix, val=val)
+
+    def empty(self):
+        """A SparseFrames of no frames with this consumer's parameters (what a run without frames writes)."""
+        return self._sparse_frames([], np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros(1, np.int64),
+                                   np.zeros(0, np.int32), np.zeros(0, np.float32))
+
+    def _peak_dict(self) -> dict:
+        if self.min_peaks <= 0:
+            return {}
+        p = self.peak_params
+        return {"thr_peak": float(p.thr_peak), "son_min": float(p.son_min), "radius": float(p.radius)}
+
+    def _count(self, sf):
+        from .sparse import FLAG_OVERFLOW, FLAG_SKIPPED
+
+        with self._lock:
+            self.frames_skipped += int(((sf.flags & FLAG_SKIPPED) != 0).sum())
+            self.frames_overflowed += int(((sf.flags & FLAG_OVERFLOW) != 0).sum())
+            self.frames_stored += int(((sf.flags & (FLAG_SKIPPED | FLAG_OVERFLOW)) == 0).sum())
+            self.pixels_stored += int(sf.offs[-1])
+            self.results.append(sf)
+
+    # ------------------------------------------------------------------ the two host steps of a GPU batch
+    def _issued(self, b: int, n: int, st, meta):
+        """Batch just launched on ``st`` (current stream): header -> pinned host, then advance the older batches."""
+        self._hdr_host[b].copy_(self._hdr[b], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(st)
+        self._pending.append({"b": b, "n": n, "st": st, "meta": meta, "hdr": ev, "data": None})
+        self._advance(keep=1)
+
+    def _advance(self, keep: int):
+        """Step every batch but the newest ``keep``: a batch whose header is awaited gets its data copy
+        issued; a batch whose data copy was issued is collected once at least one newer batch is behind
+        it (or on a flush, keep = 0)."""
+        B = self.batch
+        for i, p in enumerate(list(self._pending)):
+            if len(self._pending) - i <= keep:
+                break
+            if p["data"] is None:
+                p["hdr"].synchronize()
+                row = self._hdr_host[p["b"]].numpy()
+                n = p["n"]
+                p["offs"] = row[:8 * (B + 1)].view(np.int64)[:n + 1].copy()
+                p["nnz"] = row[8 * (B + 1):8 * (B + 1) + 4 * B].view(np.int32)[:n].copy()
+                p["flags"] = row[8 * (B + 1) + 4 * B:self._hdr_bytes][:n].copy()
+                total = int(p["offs"][n])
+                p["pix"] = torch.empty(total, dtype=torch.int32, pin_memory=total > 0)
+                p["val"] = torch.empty(total, dtype=torch.float32, pin_memory=total > 0)
+                ev = torch.cuda.Event()
+                with torch.cuda.stream(p["st"]):   # exactly offs[F] elements, never the full capacity
+                    if total:
+                        p["pix"].copy_(self._pix[p["b"], :total], non_blocking=True)
+                        p["val"].copy_(self._val[p["b"], :total], non_blocking=True)
+                    ev.record(p["st"])
+                p["data"] = ev
+        while self._pending and self._pending[0]["data"] is not None and len(self._pending) > 2 * keep:
+            p = self._pending.popleft()
+            p["data"].synchronize()
+            self._count(self._sparse_frames(p["meta"], p["nnz"], p["flags"], p["offs"], p["pix"].numpy().copy(),
+                                            p["val"].numpy().copy()))
+
+    # ------------------------------------------------------------------ processing
+    def process_frames(self, frames, meta):
+        """Sparsify ``frames`` (tensors of n elements on this consumer's device, issued on the current
+        stream) that are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank,
+        idx, gevt, photon_energy)``.  GPU: returns the consumer stream the batch runs on."""
+        n = len(frames)
+        if n == 0:
+            return None
+        if n > self.batch:
+            raise ValueError(f"sparse: {n} frames in a batch of at most {self.batch}")
+        meta = [tuple(m) + (None,) * (4 - len(m)) for m in meta]
+        st = None
+        if self.gpu:
+            b, k, st = self._next()
+            offs, nnz, flags = self._views(b, n)
+            st.wait_stream(torch.cuda.current_stream(self.device))   # the frames were produced / leased on it
+            with torch.cuda.stream(st):
+                fl = [t.reshape(-1) for t in frames]
+                keys = None
+                if self.min_peaks > 0:
+                    keys = self._counts[b, :n]
+                    kernels.peakfind([t.reshape(self._pf_shape) for t in frames], self._pf_shape, self.peak_params,
+                                     self._peaks[b, :n], keys, self._summary[b, :n], st, total=self._pf_total,
+                                     scratch=self._pf_scratch[k])
+                kernels.sparsify(fl, self.thr, self.vmax, self.cap, nnz, flags, offs, self._pix[b], self._val[b],
+                                 mask=self._mask, keys=keys, key_min=self.min_peaks, scratch=self._scratch[k], stream=st)
+                self._issued(b, n, st, meta)
+        else:
+            from .ops import reference
+
+            x = torch.stack([t.reshape(-1) for t in frames])
+            keys = None
+            if self.min_peaks > 0:
+                pk, _ = reference.peakfind_reference(x.reshape(n, *self._pf_shape), self.peak_params)
+                keys = torch.tensor([int(p.shape[0]) for p in pk], dtype=torch.int32)
+            nnz, flags, offs, pix, val = reference.sparsify_reference(x, self.thr, self.vmax, self.cap,
+                                                                      mask=self._mask_np, keys=keys,
+                                                                      key_min=self.min_peaks)
+            self._count(self._sparse_frames(meta, nnz.numpy(), flags.numpy(), offs.numpy(), pix.numpy(), val.numpy()))
+        self.frames += n
+        return st
+
+    def process(self, items: List[FrameItem]):
+        if not items:
+            return
+        st = self.process_frames([it.data for it in items],
+                                 [(it.rank, it.idx, it.gevt, it.photon_energy) for it in items])
+        for it in items:
+            it.release(st) if self.gpu else it.release()
+
+    def poll(self, timeout: float = 0.05, max_items: Optional[int] = None) -> int:
+        """Take up to ``batch`` ready frames (waiting up to ``timeout`` for the first) and process
+        them.  Returns frames processed; raises EndOfStream at the end of the stream."""
+        n_max = self.batch if max_items is None else max(1, min(self.batch, max_items))
+        if not self.gpu:
+            items: List[FrameItem] = []
+            it = self.ep.get(timeout=timeout)
+            if it is None:
+                return 0
+            items.append(it)
+            while len(items) < n_max:
+                try:
+                    nxt = self.ep.get(timeout=0.0)
+                except EndOfStream:
+                    break
+                if nxt is None:
+                    break
+                items.append(nxt)
+            self.process(items)
+            return len(items)
+        # GPU: one native call to lease, one per kernel family (peak finder; clear + scan + pack), one to release
+        st = self.streams[self._b % len(self.streams)]
+        slots = self.ep.get_batch(n_max, timeout, st)
+        n = len(slots)
+        if n == 0:
+            return 0
+        C = _ext.load()
+        b, k, st = self._next()
+        offs, nnz, flags = self._views(b, n)
+        sh = int(st.cuda_stream)
+        with trace_range("consumer.sparse_batch"):
+            keys = 0
+            if self.min_peaks > 0:
+                P, H, W = self._pf_shape
+                p = self.peak_params
+                C.peakfind_slots(self.ep.pool, self.ep._slot_bytes, slots, P, H, W, float(p.thr_peak), float(p.son_min),
+                                 int(p.radius), int(p.max_peaks), int(self._peaks[b].data_ptr()),
+                                 int(self._counts[b].data_ptr()), int(self._summary[b].data_ptr()),
+                                 int(self._pf_total.data_ptr()), sh, int(self._pf_scratch[k].data_ptr()))
+                keys = int(self._counts[b].data_ptr())
+            C.sparsify_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.thr, self.vmax, self.cap,
+                             0 if self._mask is None else int(self._mask.data_ptr()), keys, self.min_peaks,
+                             int(nnz.data_ptr()), int(flags.data_ptr()), int(offs.data_ptr()),
+                             int(self._pix[b].data_ptr()), int(self._val[b].data_ptr()),
+                             int(self._scratch[k].data_ptr()), self._scratch[k].numel(), sh)
+        self.ep.release_batch(slots, st)   # after the scan; the copies below read our own buffers
+        hs = self.ep.pool.headers(slots)
+        meta = [(h.rank, h.idx, h.gevt, None if h.photon_energy != h.photon_energy else h.photon_energy) for h in hs]
+        with torch.cuda.stream(st):
+            self._issued(b, n, st, meta)
+        self.frames += n
+        return n
+
+    def take_results(self) -> list:
+        """The finished batches collected so far (oldest first); they are removed from :attr:`results`."""
+        with self._lock:
+            out, self.results = self.results, []
+        return out
+
+    def metrics(self) -> dict:
+        return {"frames_consumed": self.frames, "frames_stored": self.frames_stored,
+                "frames_skipped": self.frames_skipped, "frames_overflowed": self.frames_overflowed,
+                "pixels_stored": self.pixels_stored}
+
+    def sync_streams(self):
+        """Host waits for every batch issued so far (both consumer streams)."""
+        if self.gpu:
+            for st in self.streams:
+                st.synchronize()
+
+    def synchronize(self):
+        """Wait for every batch and collect it.  Returns the list of finished batches not taken yet."""
+        if self.gpu:
+            self._advance(keep=0)
+            self._advance(keep=0)   # first pass issues the last data copies, second collects them
+            self.sync_streams()
+        return self.results

@@ -77,10 +77,15 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--data_dir", type=str, default=None, help="raw-run files directory (or $PSANA_RAY_DATA)")
     g.add_argument("--chunk", type=int, default=64, help="frames per H2D copy / kernel launch (<= 64)")
     g.add_argument("--route", type=str, default="balanced", choices=["balanced", "local_first", "spread"])
-    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark"],
+    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse"],
                    help="also consume on every producer rank (co-located consumer, BASELINE config 5): the K-07 "
-                        "peak finder, the K-08 radial profile (default binning of psana-ray-consumer), or the K-09 "
-                        "dark statistics (needs --mode raw; --out_dark writes the file)")
+                        "peak finder, the K-08 radial profile (default binning of psana-ray-consumer), the K-09 "
+                        "dark statistics (needs --mode raw; --out_dark writes the file), or the K-10 zero "
+                        "suppression (--out_sparse writes the file; --sparse_thr ... --min_peaks as for "
+                        "psana-ray-consumer --task sparse)")
+    g.add_argument("--out_sparse", type=str, default=None,
+                   help="--consumer_task sparse: write the rank's sparse frames (psana_ray_amd.sparse.SparseFrames "
+                        ".npz) here")
     g.add_argument("--out_dark", type=str, default=None,
                    help="--consumer_task dark: write the rank's dark statistics (psana_ray_amd.dark.DarkStats .npz) here")
     g.add_argument("--constants", type=str, default=None,
@@ -109,6 +114,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "the SDMA engines (utils/runtime_env.py)")
     g.add_argument("--local", action="store_true",
                    help="single-process queue: no rendezvous; requires --consumer_task (no external consumers)")
+    from .consumer import add_sparse_arguments
+
+    add_sparse_arguments(parser)
     return parser
 
 
@@ -236,7 +244,8 @@ def main(argv=None) -> int:
 
     from .models.detector import Mode
     from .parallel.launch import bind_numa_to_device, detect, device_for
-    from .pipeline import DarkStatsConsumer, PeakFinderConsumer, ProducerPipeline, RadialProfileConsumer
+    from .pipeline import (DarkStatsConsumer, PeakFinderConsumer, ProducerPipeline, RadialProfileConsumer,
+                           SparseFrameConsumer)
     from .queue.endpoint import EndOfStream, QueueEndpoint
     from .queue.ring import FrameRing, physical_slots
     from .queue.session import QueueSession
@@ -274,6 +283,12 @@ def main(argv=None) -> int:
         return 2
     if args.consumer_task == "dark" and (mode != Mode.raw or int(args.panel_shards) > 1):
         log.error("--consumer_task dark needs whole raw frames (--mode raw, no --panel_shards)")
+        return 2
+    if args.consumer_task == "sparse" and (mode == Mode.raw or int(args.panel_shards) > 1):
+        log.error("--consumer_task sparse needs whole calibrated frames (not --mode raw / --panel_shards)")
+        return 2
+    if args.out_sparse is not None and args.consumer_task != "sparse":
+        log.error("--out_sparse belongs to --consumer_task sparse")
         return 2
     if args.out_dark is not None and args.consumer_task != "dark":
         log.error("--out_dark belongs to --consumer_task dark")
@@ -402,6 +417,22 @@ def main(argv=None) -> int:
                 cons = RadialProfileConsumer(ep, RadialBinning.from_geometry(geo, mode, 512))
             elif args.consumer_task == "dark":
                 cons = DarkStatsConsumer(ep, source.consts.spec)
+            elif args.consumer_task == "sparse":
+                from .consumer import SparseWriter, load_sparse_mask
+
+                try:
+                    smask = load_sparse_mask(args.sparse_mask, frame_shape)
+                    cons = SparseFrameConsumer(ep, frame_shape, thr=args.sparse_thr, vmax=args.sparse_vmax,
+                                               cap=args.sparse_cap, mask=smask, min_peaks=args.min_peaks,
+                                               detector=args.detector_name, layout=mode.value)
+                except (ValueError, OSError) as e:
+                    log.error("--consumer_task sparse: %s", e)
+                    return 2
+                spath = args.out_sparse
+                if spath and size > 1:   # one file per rank (they join: python -m psana_ray_amd.sparse merge)
+                    root, ext = os.path.splitext(spath)
+                    spath = f"{root}.r{rank}{ext}"
+                swriter = SparseWriter(spath, args.part_frames)
             else:
                 cons = PeakFinderConsumer(ep, frame_shape, PeakFinderParams())
             registry.register("consumer", cons.metrics)
@@ -412,7 +443,14 @@ def main(argv=None) -> int:
                         cons.poll(timeout=0.1)
                     except EndOfStream:
                         break
-                if args.consumer_task == "radial":
+                    if args.consumer_task == "sparse":
+                        swriter.add(cons.take_results())
+                if args.consumer_task == "sparse":
+                    cons.synchronize()
+                    swriter.add(cons.take_results())
+                    swriter.close(cons.empty())
+                    stats["sparse"] = cons.metrics()
+                elif args.consumer_task == "radial":
                     stats["radial"] = cons.synchronize()
                 elif args.consumer_task == "dark":
                     stats["dark"] = cons.stats()
@@ -460,6 +498,13 @@ def main(argv=None) -> int:
                         path = args.out_dark if size == 1 else f"{root}.r{rank}{ext}"
                         ds.save(path)
                         log.info("Rank %d: dark statistics written to %s", rank, path)
+                elif args.consumer_task == "sparse":
+                    m = stats.get("sparse", {})
+                    print(f"Consumer {rank} sparse: frames={stats.get('consumed', 0)} stored={m.get('frames_stored', 0)} "
+                          f"skipped={m.get('frames_skipped', 0)} overflowed={m.get('frames_overflowed', 0)} "
+                          f"pixels={m.get('pixels_stored', 0)}", flush=True)
+                    if swriter.paths:
+                        log.info("Rank %d: sparse frames written to %s", rank, ", ".join(swriter.paths))
                 else:
                     log.info("Rank %d: co-located consumer processed %d frames, %d peaks", rank,
                              stats.get("consumed", 0), stats.get("peaks", 0))
