@@ -97,6 +97,22 @@ static FramePtrs make_ptrs(const std::vector<uint64_t>& in, const std::vector<ui
   return fp;
 }
 
+// The consumers' ring-slot bindings (peakfind_slots, radial_slots, dark_slots, sparsify_slots): the two
+// checks they share, then fn(index of the chunk's first slot, its slot pointers) for every chunk of at
+// most kMaxFrames slots.
+template <class Fn>
+static void for_slot_chunks(const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots,
+                            int64_t frame_bytes, const char* name, Fn&& fn) {
+  const int ns = (int)slots.size();
+  if (ns < 1) pr::check(false, std::string(name) + ": no slots");
+  if (slot_bytes < frame_bytes) pr::check(false, std::string(name) + ": frame larger than a slot");
+  for (int a = 0; a < ns; a += pr::kMaxFrames) {
+    std::vector<uint64_t> in(std::min(pr::kMaxFrames, ns - a));
+    for (size_t i = 0; i < in.size(); ++i) in[i] = pool.slot_ptr(slots[a + i]);
+    fn(a, in);
+  }
+}
+
 // Diagnostic (PSANA_RAY_AMD_SEGV_TRACE=1): a SIGSEGV prints the native stack first, then the
 // handler that was installed before (Python's faulthandler, or the default) runs on the re-fault.
 static struct sigaction g_prev_segv;
@@ -302,18 +318,14 @@ PYBIND11_MODULE(_C, m) {
         [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int n_panels, int rows,
            int cols, float thr_peak, float son_min, int radius, int max_peaks, uint64_t peaks, uint64_t counts,
            uint64_t summary, uint64_t total, uint64_t stream, uint64_t scratch) {
-          const int n = (int)slots.size();
-          pr::check(n >= 1, "peakfind_slots: no slots");
-          pr::check(slot_bytes >= (int64_t)n_panels * rows * cols * 4, "peakfind_slots: frame larger than a slot");
           pr::check(scratch != 0, "peakfind_slots: needs a zero-initialised scratch block (PF_SCRATCH_BYTES)");
-          for (int a = 0; a < n; a += pr::kMaxFrames) {
-            const int m = std::min(pr::kMaxFrames, n - a);
-            std::vector<uint64_t> in(m);
-            for (int i = 0; i < m; ++i) in[i] = pool.slot_ptr(slots[a + i]);
-            pr::launch_peakfind(make_ptrs(in, in), m, n_panels, rows, cols, thr_peak, son_min, radius, max_peaks,
-                                peaks + (uint64_t)a * max_peaks * 32, counts + (uint64_t)a * 4,
-                                summary + (uint64_t)a * 8, total, stream, scratch);
-          }
+          for_slot_chunks(pool, slot_bytes, slots, (int64_t)n_panels * rows * cols * 4, "peakfind_slots",
+                          [&](int a, const std::vector<uint64_t>& in) {
+                            pr::launch_peakfind(make_ptrs(in, in), (int)in.size(), n_panels, rows, cols, thr_peak,
+                                                son_min, radius, max_peaks, peaks + (uint64_t)a * max_peaks * 32,
+                                                counts + (uint64_t)a * 4, summary + (uint64_t)a * 8, total, stream,
+                                                scratch);
+                          });
         },
         py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("n_panels"), py::arg("rows"),
         py::arg("cols"), py::arg("thr_peak"), py::arg("son_min"), py::arg("radius"), py::arg("max_peaks"),
@@ -336,17 +348,11 @@ PYBIND11_MODULE(_C, m) {
         [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int64_t n, uint64_t bins,
            int nbins, float vmin, float vmax, int frac_bits, uint64_t sums, uint64_t counts, uint64_t profile,
            uint64_t run, uint64_t stream) {
-          const int ns = (int)slots.size();
-          pr::check(ns >= 1, "radial_slots: no slots");
-          pr::check(slot_bytes >= n * 4, "radial_slots: frame larger than a slot");
-          for (int a = 0; a < ns; a += pr::kMaxFrames) {
-            const int m = std::min(pr::kMaxFrames, ns - a);
-            std::vector<uint64_t> in(m);
-            for (int i = 0; i < m; ++i) in[i] = pool.slot_ptr(slots[a + i]);
+          for_slot_chunks(pool, slot_bytes, slots, n * 4, "radial_slots", [&](int a, const std::vector<uint64_t>& in) {
             const uint64_t row = (uint64_t)a * nbins;
-            pr::launch_radial(make_ptrs(in, in), m, n, bins, nbins, vmin, vmax, frac_bits, sums + row * 8,
-                              counts + row * 4, profile + row * 4, run, stream);
-          }
+            pr::launch_radial(make_ptrs(in, in), (int)in.size(), n, bins, nbins, vmin, vmax, frac_bits,
+                              sums + row * 8, counts + row * 4, profile + row * 4, run, stream);
+          });
         },
         py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("n"), py::arg("bins"), py::arg("nbins"),
         py::arg("vmin"), py::arg("vmax"), py::arg("frac_bits"), py::arg("sums"), py::arg("counts"),
@@ -364,15 +370,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("dark_slots",
         [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int64_t n, int kind,
            int adu_lo, int adu_hi, uint64_t cnt, uint64_t sum, uint64_t sq, uint64_t stream) {
-          const int ns = (int)slots.size();
-          pr::check(ns >= 1, "dark_slots: no slots");
-          pr::check(slot_bytes >= n * 2, "dark_slots: frame larger than a slot");
-          for (int a = 0; a < ns; a += pr::kMaxFrames) {
-            const int m = std::min(pr::kMaxFrames, ns - a);
-            std::vector<uint64_t> in(m);
-            for (int i = 0; i < m; ++i) in[i] = pool.slot_ptr(slots[a + i]);
-            pr::launch_dark(make_ptrs(in, in), m, n, kind, adu_lo, adu_hi, cnt, sum, sq, stream);
-          }
+          for_slot_chunks(pool, slot_bytes, slots, n * 2, "dark_slots", [&](int, const std::vector<uint64_t>& in) {
+            pr::launch_dark(make_ptrs(in, in), (int)in.size(), n, kind, adu_lo, adu_hi, cnt, sum, sq, stream);
+          });
         },
         py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("n"), py::arg("kind"), py::arg("adu_lo"),
         py::arg("adu_hi"), py::arg("cnt"), py::arg("sum"), py::arg("sq"), py::arg("stream"),
@@ -396,13 +396,12 @@ PYBIND11_MODULE(_C, m) {
         [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int64_t n, float thr,
            float vmax, int64_t cap, uint64_t mask, uint64_t keys, int key_min, uint64_t nnz, uint64_t flags,
            uint64_t offs, uint64_t pix, uint64_t val, uint64_t scratch, int64_t scratch_bytes, uint64_t stream) {
-          const int ns = (int)slots.size();
+          const int ns = (int)slots.size();   // one launch: the batch's offs / pix / val are packed together
           pr::check(ns >= 1 && ns <= pr::kMaxFrames, "sparsify_slots: 1..64 slots per batch");
-          pr::check(slot_bytes >= n * 4, "sparsify_slots: frame larger than a slot");
-          std::vector<uint64_t> in(ns);
-          for (int i = 0; i < ns; ++i) in[i] = pool.slot_ptr(slots[i]);
-          pr::launch_sparsify(make_ptrs(in, in), ns, n, thr, vmax, cap, mask, keys, key_min, nnz, flags, offs, pix,
-                              val, scratch, scratch_bytes, stream);
+          for_slot_chunks(pool, slot_bytes, slots, n * 4, "sparsify_slots", [&](int, const std::vector<uint64_t>& in) {
+            pr::launch_sparsify(make_ptrs(in, in), (int)in.size(), n, thr, vmax, cap, mask, keys, key_min, nnz, flags,
+                                offs, pix, val, scratch, scratch_bytes, stream);
+          });
         },
         py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("n"), py::arg("thr"), py::arg("vmax"),
         py::arg("cap"), py::arg("mask"), py::arg("keys"), py::arg("key_min"), py::arg("nnz"), py::arg("flags"),

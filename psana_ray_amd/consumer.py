@@ -156,23 +156,64 @@ def radial_binning(args, detector_name: str, layout: str, frame_shape):
     return rb
 
 
+def _has_whole_frames(reader, task: str, what: str) -> bool:
+    """The guards of the tasks that run a pipeline consumer on whole frames: False, after logging why,
+    without the distributed queue or on a queue of panel shards (the caller returns 2)."""
+    if reader.endpoint is None:
+        log.error("--task %s needs the distributed queue (a producer session)", task)
+        return False
+    if reader.panel_shards > 1:
+        log.error("--task %s: the producers queue panel shards (--panel_shards %d); %s need whole frames (out of "
+                  "scope)", task, reader.panel_shards, what)
+        return False
+    return True
+
+
+def _drive(args, reader, stop, progress, cons, raw_meta=None, each=None) -> int:
+    """Feed ``cons`` until the end of the stream, ``stop`` or --max_frames; ``progress["n"]`` counts
+    frames.  raw_meta: None to poll the queue; on a raw ring (--calibrate_on_read) the function that
+    gives an item's meta tuple -- the items are calibrated here, then processed.  each: called after
+    every iteration.  Returns 0, or 1 when the queue died."""
+    from .data_reader import DataReaderError, EndOfStream
+    from .queue.endpoint import EndOfStream as QueueEOS
+    from .queue.endpoint import QueuePeerError
+
+    rc = 0
+    try:
+        while not stop["flag"] and (args.max_frames is None or progress["n"] < args.max_frames):
+            left = None if args.max_frames is None else args.max_frames - progress["n"]
+            if raw_meta is None:
+                cons.poll(timeout=1.0, max_items=left)
+            else:
+                items = reader.read_batch(cons.batch if left is None else min(cons.batch, left), timeout=1.0)
+                if items:
+                    meta = [raw_meta(it) for it in items]
+                    frames = reader.calibrate(items)
+                    st = cons.process_frames([frames[i] for i in range(len(items))], meta)
+                    if st is not None:
+                        frames.record_stream(st)
+            progress["n"] = cons.frames
+            if each is not None:
+                each()
+    except (EndOfStream, QueueEOS):
+        log.info("Consumer %s: end of stream", reader.consumer_id)
+    except (DataReaderError, QueuePeerError) as e:
+        print(f"DataReader error: {e}")
+        print("Queue actor is dead. Exiting...")
+        rc = 1
+    progress["n"] = cons.frames
+    return rc
+
+
 def run_radial(args, reader, stop, progress) -> int:
     """--task radial: integrate until the end of the stream; ``progress["n"]`` counts frames."""
     import torch
 
     from . import radial
-    from .data_reader import DataReaderError, EndOfStream
     from .pipeline import RadialProfileConsumer
-    from .queue.endpoint import EndOfStream as QueueEOS
-    from .queue.endpoint import QueuePeerError
 
     cid = reader.consumer_id
-    if reader.endpoint is None:
-        log.error("--task radial needs the distributed queue (a producer session)")
-        return 2
-    if reader.panel_shards > 1:
-        log.error("--task radial: the producers queue panel shards (--panel_shards %d); radial profiles need whole "
-                  "frames (out of scope)", reader.panel_shards)
+    if not _has_whole_frames(reader, "radial", "radial profiles"):
         return 2
     det = (reader.session_meta or {}).get("detector") or {}
     name = det.get("name") or args.detector_name
@@ -199,28 +240,8 @@ def run_radial(args, reader, stop, progress) -> int:
     except (ValueError, KeyError) as e:
         log.error("--task radial: %s", e)
         return 2
-    rc = 0
-    try:
-        while not stop["flag"] and (args.max_frames is None or progress["n"] < args.max_frames):
-            left = None if args.max_frames is None else args.max_frames - progress["n"]
-            if cal is None:
-                cons.poll(timeout=1.0, max_items=left)
-            else:   # raw ring (--calibrate_on_read): calibrate here, then integrate
-                items = reader.read_batch(cons.batch if left is None else min(cons.batch, left), timeout=1.0)
-                if items:
-                    meta = [(it.rank, it.idx, it.gevt) for it in items]
-                    frames = reader.calibrate(items)
-                    st = cons.process_frames([frames[i] for i in range(len(items))], meta)
-                    if st is not None:
-                        frames.record_stream(st)
-            progress["n"] = cons.frames
-    except (EndOfStream, QueueEOS):
-        log.info("Consumer %s: end of stream", cid)
-    except (DataReaderError, QueuePeerError) as e:
-        print(f"DataReader error: {e}")
-        print("Queue actor is dead. Exiting...")
-        rc = 1
-    progress["n"] = cons.frames
+    rc = _drive(args, reader, stop, progress, cons,
+                raw_meta=None if cal is None else lambda it: (it.rank, it.idx, it.gevt))
     run_sum, run_count, frames = cons.synchronize()
     print(f"Consumer {cid} radial: frames={frames} nbins={binning.nbins} unit={binning.unit} layout={layout} "
           f"detector={name} pixels={int(run_count.sum())}", flush=True)
@@ -235,19 +256,11 @@ def run_dark(args, reader, stop, progress) -> int:
     as they are: a --calibrate_on_read queue's raw items are NOT calibrated)."""
     import torch
 
-    from .data_reader import DataReaderError, EndOfStream
     from .models import get_detector
     from .pipeline import DarkStatsConsumer
-    from .queue.endpoint import EndOfStream as QueueEOS
-    from .queue.endpoint import QueuePeerError
 
     cid = reader.consumer_id
-    if reader.endpoint is None:
-        log.error("--task dark needs the distributed queue (a producer session)")
-        return 2
-    if reader.panel_shards > 1:
-        log.error("--task dark: the producers queue panel shards (--panel_shards %d); dark statistics need whole "
-                  "frames (out of scope)", reader.panel_shards)
+    if not _has_whole_frames(reader, "dark", "dark statistics"):
         return 2
     name = ((reader.session_meta or {}).get("detector") or {}).get("name") or args.detector_name
     if not name:
@@ -263,19 +276,7 @@ def run_dark(args, reader, stop, progress) -> int:
     except (ValueError, KeyError) as e:
         log.error("--task dark: %s", e)
         return 2
-    rc = 0
-    try:
-        while not stop["flag"] and (args.max_frames is None or progress["n"] < args.max_frames):
-            left = None if args.max_frames is None else args.max_frames - progress["n"]
-            cons.poll(timeout=1.0, max_items=left)
-            progress["n"] = cons.frames
-    except (EndOfStream, QueueEOS):
-        log.info("Consumer %s: end of stream", cid)
-    except (DataReaderError, QueuePeerError) as e:
-        print(f"DataReader error: {e}")
-        print("Queue actor is dead. Exiting...")
-        rc = 1
-    progress["n"] = cons.frames
+    rc = _drive(args, reader, stop, progress, cons)   # always polls: raw items are what it wants
     st = cons.stats()
     print(f"Consumer {cid} dark: frames={st.frames} detector={name} window=[{st.adu_lo},{st.adu_hi}] "
           f"samples={int(st.cnt.sum())} per_candidate={[int(c) for c in st.cnt.sum(axis=1)]}", flush=True)
@@ -402,18 +403,10 @@ def sparse_layout(reader, args):
 def run_sparse(args, reader, stop, progress) -> int:
     """--task sparse: zero-suppress until the end of the stream; ``progress["n"]`` counts frames."""
     from .config import PeakFinderParams
-    from .data_reader import DataReaderError, EndOfStream
     from .pipeline import SparseFrameConsumer
-    from .queue.endpoint import EndOfStream as QueueEOS
-    from .queue.endpoint import QueuePeerError
 
     cid = reader.consumer_id
-    if reader.endpoint is None:
-        log.error("--task sparse needs the distributed queue (a producer session)")
-        return 2
-    if reader.panel_shards > 1:
-        log.error("--task sparse: the producers queue panel shards (--panel_shards %d); sparse frames need whole "
-                  "frames (out of scope)", reader.panel_shards)
+    if not _has_whole_frames(reader, "sparse", "sparse frames"):
         return 2
     cal = reader.calibrator
     try:
@@ -427,29 +420,9 @@ def run_sparse(args, reader, stop, progress) -> int:
         log.error("--task sparse: %s", e)
         return 2
     writer = SparseWriter(args.out, args.part_frames)
-    rc = 0
-    try:
-        while not stop["flag"] and (args.max_frames is None or progress["n"] < args.max_frames):
-            left = None if args.max_frames is None else args.max_frames - progress["n"]
-            if cal is None:
-                cons.poll(timeout=1.0, max_items=left)
-            else:   # raw ring (--calibrate_on_read): calibrate here, then sparsify
-                items = reader.read_batch(cons.batch if left is None else min(cons.batch, left), timeout=1.0)
-                if items:
-                    meta = [(it.rank, it.idx, it.gevt, it.photon_energy) for it in items]
-                    frames = reader.calibrate(items)
-                    st = cons.process_frames([frames[i] for i in range(len(items))], meta)
-                    if st is not None:
-                        frames.record_stream(st)
-            progress["n"] = cons.frames
-            writer.add(cons.take_results())
-    except (EndOfStream, QueueEOS):
-        log.info("Consumer %s: end of stream", cid)
-    except (DataReaderError, QueuePeerError) as e:
-        print(f"DataReader error: {e}")
-        print("Queue actor is dead. Exiting...")
-        rc = 1
-    progress["n"] = cons.frames
+    rc = _drive(args, reader, stop, progress, cons,
+                raw_meta=None if cal is None else lambda it: (it.rank, it.idx, it.gevt, it.photon_energy),
+                each=lambda: writer.add(cons.take_results()))
     cons.synchronize()
     writer.add(cons.take_results())
     writer.close(cons.empty())
@@ -495,26 +468,11 @@ def main(argv=None) -> int:
         reporter = Reporter(registry, rank=cid if cid is not None else 0, interval=args.metrics_interval,
                             json_path=args.metrics_json).start()
         pf = None
-        if args.task == "radial":
+        run_task = {"radial": run_radial, "dark": run_dark, "sparse": run_sparse}.get(args.task)
+        if run_task is not None:   # the tasks that run a pipeline consumer to the end of the stream
             progress = {"n": 0}
-            registry.register("radial", lambda: {"frames_consumed": progress["n"]})
-            rc = run_radial(args, reader, stop, progress)
-            n = progress["n"]
-            if rc:
-                reporter.stop(final_sample=False)
-                return rc
-        if args.task == "dark":
-            progress = {"n": 0}
-            registry.register("dark", lambda: {"frames_consumed": progress["n"]})
-            rc = run_dark(args, reader, stop, progress)
-            n = progress["n"]
-            if rc:
-                reporter.stop(final_sample=False)
-                return rc
-        if args.task == "sparse":
-            progress = {"n": 0}
-            registry.register("sparse", lambda: {"frames_consumed": progress["n"]})
-            rc = run_sparse(args, reader, stop, progress)
+            registry.register(args.task, lambda: {"frames_consumed": progress["n"]})
+            rc = run_task(args, reader, stop, progress)
             n = progress["n"]
             if rc:
                 reporter.stop(final_sample=False)
@@ -558,7 +516,8 @@ def main(argv=None) -> int:
                 import torch.distributed as dist
 
                 dist.destroy_process_group()
-        while args.task not in ("train", "radial", "dark", "sparse") and not stop["flag"] and (args.max_frames is None or n < args.max_frames):
+        reads_here = args.task in ("print", "peakfind", "none")   # the tasks above ran to their end already
+        while reads_here and not stop["flag"] and (args.max_frames is None or n < args.max_frames):
             try:
                 if args.task == "peakfind" and reader.endpoint is not None:
                     items = reader.read_batch(args.batch, timeout=1.0)

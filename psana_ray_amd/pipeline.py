@@ -480,81 +480,52 @@ def _make_streams(device, n: int, kind: str, owner=None):
     return out
 
 
-class PeakFinderConsumer:
-    """Consumer engine: batches of leased slots -> K-07 peak finder -> stream-ordered release.
+class _BatchConsumer:
+    """What the consumer engines share: batches of leased ring slots -> one native call on a consumer
+    stream -> stream-ordered release.  A consumer adds its buffers, ``synchronize()`` and the hooks
+    at the end of this class.
 
-    GPU: consecutive batches alternate between TWO consumer streams, each with its own peak-finder
-    scratch, so one launch's candidate-test tail (every workgroup tests its parked candidates after
-    its stream of reads) overlaps the next launch's streaming reads instead of idling HBM."""
+    GPU: consecutive batches alternate between the consumer streams (two by default), so one launch's
+    tail overlaps the next launch's streaming reads instead of idling HBM.  The orderings every
+    consumer relies on are stated here once:
+      * :meth:`poll` leases on the stream that :meth:`_next` then hands out, and the batch counter
+        advances after a non-empty lease only (an empty poll uses no buffer row);
+      * the ring slots go back stream-ordered right after the kernels that read them: whatever
+        ``_launched`` issues afterwards reads the consumer's own buffers, never a ring slot;
+      * the slot headers (a host read) are taken before the release.
+    CPU endpoints run the golden models (ops.reference)."""
 
-    def __init__(self, endpoint: QueueEndpoint, frame_shape, params: Optional[PeakFinderParams] = None,
-                 batch: Optional[int] = None, keep_results: bool = False, stream_kind: str = CONSUMER_STREAM_KIND,
-                 streams: int = CONSUMER_STREAMS, ranks_per_gpu: Optional[int] = None):
-        """batch: frames per peak-finder launch; None -> config.pipeline_shape for the ranks sharing
-        this GPU (``ranks_per_gpu``; None: parallel.launch.ranks_per_gpu())."""
+    name = ""            # the trace range of a batch is "consumer.<name>_batch"
+    wants_meta = False   # True: _launched(b, n, st, meta) runs after every launch (results are kept)
+
+    def __init__(self, endpoint: QueueEndpoint, batch: Optional[int], ranks_per_gpu: Optional[int], streams: int,
+                 stream_kind: str):
+        """batch: frames per launch; None -> config.pipeline_shape for the ranks sharing this GPU
+        (``ranks_per_gpu``; None: parallel.launch.ranks_per_gpu())."""
         self.ep = endpoint
-        self.params = params or PeakFinderParams()
-        self.batch = min(resolve_consumer_batch(batch, ranks_per_gpu), kernels.MAX_FRAMES)
         self.device = endpoint.ring.device
         self.gpu = self.device.type == "cuda"
-        self.shape = tuple(frame_shape)
+        self.batch = min(resolve_consumer_batch(batch, ranks_per_gpu), kernels.MAX_FRAMES)
         self.frames = 0
-        self.peaks_total = 0
-        self.keep_results = keep_results
-        self.results = []
-        if self.gpu:
-            self.streams = _make_streams(self.device, int(streams), stream_kind, owner=self)
-            self.stream = self.streams[0]
-            B = self.batch
-            # buffer k % nbuf is reused by launch k + nbuf, on the same stream as k
-            self._nbuf = 2 * len(self.streams)
-            self.peaks = torch.empty((self._nbuf, B, self.params.max_peaks, 8), dtype=torch.float32, device=self.device)
-            # counts [B] int32 and summary [B, 2] f32 of a batch share one row; the peak finder
-            # writes them whole from its self-resetting scratch (no per-batch fill)
-            self._meta = torch.zeros((self._nbuf, 3 * B), dtype=torch.int32, device=self.device)
-            # one scratch block per stream (a block must never serve two launches in flight)
-            self._pf_scratch = [torch.zeros(kernels.PF_SCRATCH_WORDS, dtype=torch.int32, device=self.device)
-                                for _ in self.streams]
-            self.counts = self._meta[:, :B]
-            self.summary = self._meta[:, B:].view(torch.float32).view(self._nbuf, B, 2)
-            self.count_acc = torch.zeros((), dtype=torch.int64, device=self.device)
-            self._b = 0
+        self.streams = _make_streams(self.device, int(streams), stream_kind, owner=self) if self.gpu else []
+        self.stream = self.streams[0] if self.gpu else None
+        self._nbuf = 2 * len(self.streams)   # rows of every per-batch buffer
+        self._b = 0                          # batches launched
+        self._trace = f"consumer.{self.name}_batch"
 
-    def process(self, items: List[FrameItem]):
-        n = len(items)
-        if n == 0:
-            return
-        if self.gpu:
-            b = self._b % self._nbuf
-            k = self._b % len(self.streams)
-            st = self.streams[k]
-            self._b += 1
-            st.wait_stream(torch.cuda.current_stream(self.device))   # the items were leased on it
-            with torch.cuda.stream(st):
-                kernels.peakfind([it.data for it in items], self.shape, self.params, self.peaks[b, :n],
-                                 self.counts[b, :n], self.summary[b, :n], st, total=self.count_acc,
-                                 scratch=self._pf_scratch[k])
-                if self.keep_results:
-                    self.results.append((self.peaks[b, :n].clone(), self.counts[b, :n].clone(),
-                                         [(it.rank, it.idx, it.gevt) for it in items]))
-            for it in items:
-                it.release(st)
-        else:
-            from .ops import reference
-
-            frames = torch.stack([it.data.reshape(self.shape) for it in items])
-            peaks, _summary = reference.peakfind_reference(frames, self.params)
-            self.peaks_total += sum(int(p.shape[0]) for p in peaks)
-            if self.keep_results:
-                self.results.append((peaks, [(it.rank, it.idx, it.gevt) for it in items]))
-            for it in items:
-                it.release()
-        self.frames += n
+    def _next(self):
+        """(buffer row, stream index, stream) of the next launch.  Row b is reused by launch
+        ``_b + _nbuf``, on the same stream (``_nbuf`` is a multiple of the stream count), so stream
+        order alone keeps a launch from overwriting a row that an earlier one still uses."""
+        b = self._b % self._nbuf
+        k = self._b % len(self.streams)
+        self._b += 1
+        return b, k, self.streams[k]
 
     def poll(self, timeout: float = 0.05, max_items: Optional[int] = None) -> int:
         """Take up to ``batch`` ready frames (waiting up to ``timeout`` for the first) and process
         them.  Returns frames processed; raises EndOfStream at the end of the stream."""
-        n_max = self.batch if max_items is None else max(1, min(self.batch, max_items))
+        n_max = self._limit(self.batch if max_items is None else max(1, min(self.batch, max_items)))
         if not self.gpu:
             items: List[FrameItem] = []
             it = self.ep.get(timeout=timeout)
@@ -571,44 +542,164 @@ class PeakFinderConsumer:
                 items.append(nxt)
             self.process(items)
             return len(items)
-        # GPU: one native call to lease, one kernel launch, one native call to release
-        k = self._b % len(self.streams)
-        st = self.streams[k]
+        # GPU: one native call to lease, one per kernel family, one to release -- no per-batch torch
+        # ops and no host sync
+        st = self.streams[self._b % len(self.streams)]   # the stream _next() hands out below
         slots = self.ep.get_batch(n_max, timeout, st)
         n = len(slots)
         if n == 0:
             return 0
         C = _ext.load()
-        b = self._b % self._nbuf
-        self._b += 1
-        sh = int(st.cuda_stream)
-        P, H, W = self.shape
-        with trace_range("consumer.peakfind_batch"):
-            # one native call: the peak finder on the ring slots with self-resetting outputs (no
-            # fill kernel), bumping the on-device running peak total (no per-batch torch ops, no
-            # host sync)
-            C.peakfind_slots(self.ep.pool, self.ep._slot_bytes, slots, P, H, W, float(self.params.thr_peak),
-                             float(self.params.son_min), int(self.params.radius), int(self.params.max_peaks),
-                             int(self.peaks[b].data_ptr()), int(self.counts[b].data_ptr()),
-                             int(self.summary[b].data_ptr()), int(self.count_acc.data_ptr()), sh,
-                             int(self._pf_scratch[k].data_ptr()))
-            if self.keep_results:
-                hs = self.ep.pool.headers(slots)
-                with torch.cuda.stream(st):
-                    self.results.append((self.peaks[b, :n].clone(), self.counts[b, :n].clone(),
-                                         [(h.rank, h.idx, h.gevt) for h in hs]))
+        b, k, st = self._next()
+        with trace_range(self._trace):
+            self._launch_slots(C, slots, b, k, st)
+        meta = self._meta_of(self.ep.pool.headers(slots)) if self.wants_meta else None
         self.ep.release_batch(slots, st)
+        if self.wants_meta:
+            with torch.cuda.stream(st):
+                self._launched(b, n, st, meta)
         self.frames += n
         return n
+
+    def process_frames(self, frames, meta=None):
+        """Process ``frames`` (tensors on this consumer's device, issued on the current stream) that
+        are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank, idx, gevt)``.
+        GPU: returns the consumer stream the batch runs on."""
+        n = len(frames)
+        if n == 0:
+            return None
+        self._check_batch(n)
+        st = None
+        if self.gpu:
+            b, k, st = self._next()
+            st.wait_stream(torch.cuda.current_stream(self.device))   # the frames were produced / leased on it
+            with torch.cuda.stream(st):
+                self._launch_tensors(list(frames), b, k, st)
+                if self.wants_meta:
+                    self._launched(b, n, st, list(meta))
+        else:
+            self._reference(frames, meta)
+        self.frames += n
+        return st
+
+    def process(self, items: List[FrameItem]):
+        if not items:
+            return
+        st = self.process_frames([it.data for it in items], self._meta_of(items))
+        for it in items:
+            it.release(st) if self.gpu else it.release()
 
     def metrics(self) -> dict:
         return {"frames_consumed": self.frames}
 
     def sync_streams(self):
-        """Host waits for every batch issued so far (both consumer streams)."""
+        """Host waits for every batch issued so far (all consumer streams)."""
+        for st in self.streams:
+            st.synchronize()
+
+    # ------------------------------------------------------------------ what a consumer fills in
+    def _limit(self, n_max: int) -> int:
+        """Frames the next poll may take at most (it may raise instead)."""
+        return n_max
+
+    def _check_batch(self, n: int):
+        """process_frames: raise if a batch of ``n`` frames cannot be taken."""
+
+    def _meta_of(self, recs):
+        """The meta tuples of queue items or slot headers."""
+        return [(r.rank, r.idx, r.gevt) for r in recs]
+
+    def _launch_slots(self, C, slots, b: int, k: int, st):
+        """The native call(s) on leased ring ``slots``: buffer row b, stream k."""
+        raise NotImplementedError
+
+    def _launch_tensors(self, frames, b: int, k: int, st):
+        """The same through ops.kernels on a list of tensors; ``st`` is the current stream."""
+        raise NotImplementedError
+
+    def _reference(self, frames, meta):
+        """CPU: the golden model on ``frames``."""
+        raise NotImplementedError
+
+    def _launched(self, b: int, n: int, st, meta):
+        """After a launch of n frames (``wants_meta``), ``st`` current: keep results.  The ring slots
+        may be released already: read this consumer's buffers only."""
+
+
+class _PeakBuffers:
+    """The peak finder's (K-07) device buffers and its two calls, for :class:`PeakFinderConsumer`
+    and the hit filter of :class:`SparseFrameConsumer`."""
+
+    def __init__(self, device, params: PeakFinderParams, shape, batch: int, nbuf: int, n_streams: int):
+        B = batch
+        self.params, self.shape = params, tuple(shape)   # (P, H, W)
+        self.peaks = torch.empty((nbuf, B, params.max_peaks, 8), dtype=torch.float32, device=device)
+        # counts [B] int32 and summary [B, 2] f32 of a batch share one row; the peak finder
+        # writes them whole from its self-resetting scratch (no per-batch fill)
+        self._meta = torch.zeros((nbuf, 3 * B), dtype=torch.int32, device=device)
+        self.counts = self._meta[:, :B]
+        self.summary = self._meta[:, B:].view(torch.float32).view(nbuf, B, 2)
+        # one scratch block per stream (a block must never serve two launches in flight)
+        self.scratch = [torch.zeros(kernels.PF_SCRATCH_WORDS, dtype=torch.int32, device=device)
+                        for _ in range(n_streams)]
+        self.total = torch.zeros((), dtype=torch.int64, device=device)   # running peak total
+
+    def launch_slots(self, C, ep, slots, b: int, k: int, st):
+        """One native call: the peak finder on the ring slots with self-resetting outputs (no fill
+        kernel), bumping the on-device running peak total."""
+        P, H, W = self.shape
+        p = self.params
+        C.peakfind_slots(ep.pool, ep._slot_bytes, slots, P, H, W, float(p.thr_peak), float(p.son_min), int(p.radius),
+                         int(p.max_peaks), int(self.peaks[b].data_ptr()), int(self.counts[b].data_ptr()),
+                         int(self.summary[b].data_ptr()), int(self.total.data_ptr()), int(st.cuda_stream),
+                         int(self.scratch[k].data_ptr()))
+
+    def launch_tensors(self, frames, b: int, k: int, st):
+        n = len(frames)
+        kernels.peakfind(frames, self.shape, self.params, self.peaks[b, :n], self.counts[b, :n], self.summary[b, :n],
+                         st, total=self.total, scratch=self.scratch[k])
+
+
+class PeakFinderConsumer(_BatchConsumer):
+    """Consumer engine: batches of leased slots -> K-07 peak finder -> stream-ordered release.
+
+    GPU: every consumer stream has its own peak-finder scratch, so one launch's candidate-test tail
+    (every workgroup tests its parked candidates after its stream of reads) overlaps the next
+    launch's streaming reads."""
+
+    name = "peakfind"
+
+    def __init__(self, endpoint: QueueEndpoint, frame_shape, params: Optional[PeakFinderParams] = None,
+                 batch: Optional[int] = None, keep_results: bool = False, stream_kind: str = CONSUMER_STREAM_KIND,
+                 streams: int = CONSUMER_STREAMS, ranks_per_gpu: Optional[int] = None):
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        self.params = params or PeakFinderParams()
+        self.shape = tuple(frame_shape)
+        self.peaks_total = 0
+        self.keep_results = self.wants_meta = keep_results
+        self.results = []
         if self.gpu:
-            for st in self.streams:
-                st.synchronize()
+            self._pf = pf = _PeakBuffers(self.device, self.params, self.shape, self.batch, self._nbuf,
+                                         len(self.streams))
+            self.peaks, self.counts, self.summary, self.count_acc = pf.peaks, pf.counts, pf.summary, pf.total
+
+    def _launch_slots(self, C, slots, b, k, st):
+        self._pf.launch_slots(C, self.ep, slots, b, k, st)
+
+    def _launch_tensors(self, frames, b, k, st):
+        self._pf.launch_tensors(frames, b, k, st)
+
+    def _launched(self, b, n, st, meta):
+        self.results.append((self.peaks[b, :n].clone(), self.counts[b, :n].clone(), meta))
+
+    def _reference(self, frames, meta):
+        from .ops import reference
+
+        peaks, _summary = reference.peakfind_reference(torch.stack([t.reshape(self.shape) for t in frames]),
+                                                       self.params)
+        self.peaks_total += sum(int(p.shape[0]) for p in peaks)
+        if self.keep_results:
+            self.results.append((peaks, meta))
 
     def synchronize(self):
         if self.gpu:
@@ -617,14 +708,16 @@ class PeakFinderConsumer:
         return self.peaks_total
 
 
-class RadialProfileConsumer:
+class RadialProfileConsumer(_BatchConsumer):
     """Consumer engine: batches of leased slots -> K-08 radial profile (csrc/radial.hip) ->
-    stream-ordered release.  Same surface and stream scheme as :class:`PeakFinderConsumer`.
+    stream-ordered release.
 
     Per frame: int64 sums / int32 counts / float32 profile ``[nbins]``; per run: the integer
     accumulator ``run_sum`` / ``run_count`` / ``frames`` kept on the device (added to by both consumer
     streams with integer atomics -- exact in any order) and brought to the host by
-    :meth:`synchronize`.  CPU endpoints run the golden model (ops.reference)."""
+    :meth:`synchronize`."""
+
+    name = "radial"
 
     def __init__(self, endpoint: QueueEndpoint, binning, vmin: Optional[float] = None, vmax: Optional[float] = None,
                  frac_bits: Optional[int] = None, batch: Optional[int] = None, keep_results: bool = False,
@@ -635,15 +728,11 @@ class RadialProfileConsumer:
         from .models import radial as _radial
         from .ops.reference import radial_bound_ok
 
-        self.ep = endpoint
         self.binning = binning
         self.nbins = int(binning.nbins)
         self.vmin = _radial.DEFAULT_VMIN if vmin is None else float(vmin)
         self.vmax = _radial.DEFAULT_VMAX if vmax is None else float(vmax)
         self.frac_bits = _radial.DEFAULT_FRAC_BITS if frac_bits is None else int(frac_bits)
-        self.batch = min(resolve_consumer_batch(batch, ranks_per_gpu), kernels.MAX_FRAMES)
-        self.device = endpoint.ring.device
-        self.gpu = self.device.type == "cuda"
         self.n = int(binning.bins.size)
         if check_ring and int(np.prod(endpoint.ring.frame_shape)) != self.n:
             raise ValueError(f"radial: binning of {self.n} elements ({binning.layout} layout) for queue frames "
@@ -652,8 +741,8 @@ class RadialProfileConsumer:
             raise ValueError("radial: empty value window or frac_bits outside [0, 60]")
         if not radial_bound_ok(self.n, self.vmin, self.vmax, self.frac_bits):
             raise ValueError("radial: max(|vmin|, |vmax|) * 2^frac_bits * n must stay below 2^53")
-        self.frames = 0
-        self.keep_results = keep_results
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        self.keep_results = self.wants_meta = keep_results
         # per batch: (profiles [n, nbins] f32 on the HOST -- pinned, filled asynchronously on the GPU
         # path: read them after sync_streams() / synchronize() --, [(rank, idx, gevt), ...])
         self.results = []
@@ -661,21 +750,28 @@ class RadialProfileConsumer:
         self.run_count = np.zeros(self.nbins, np.int64)
         self.run_frames = 0
         if self.gpu:
-            self.streams = _make_streams(self.device, int(streams), stream_kind, owner=self)
-            self.stream = self.streams[0]
             B, nb = self.batch, self.nbins
-            self._nbuf = 2 * len(self.streams)   # buffer k % nbuf is reused by launch k + nbuf, on k's stream
             self.sums = torch.zeros((self._nbuf, B, nb), dtype=torch.int64, device=self.device)
             self.counts = torch.zeros((self._nbuf, B, nb), dtype=torch.int32, device=self.device)
             self.profile = torch.zeros((self._nbuf, B, nb), dtype=torch.float32, device=self.device)
             self.run = torch.zeros(2 * nb + 1, dtype=torch.int64, device=self.device)
             self.bins = binning.bins_tensor(self.device)
             kernels._validate_bin_map(self.bins, self.n, nb, self.device, "radial")
-            self._b = 0
         else:
             self._bins_cpu = torch.from_numpy(binning.bins.astype(np.int64))
 
-    def _keep(self, b: int, n: int, meta):
+    def _launch_slots(self, C, slots, b, k, st):
+        C.radial_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, int(self.bins.data_ptr()), self.nbins,
+                       self.vmin, self.vmax, self.frac_bits, int(self.sums[b].data_ptr()),
+                       int(self.counts[b].data_ptr()), int(self.profile[b].data_ptr()), int(self.run.data_ptr()),
+                       int(st.cuda_stream))
+
+    def _launch_tensors(self, frames, b, k, st):
+        n = len(frames)
+        kernels.radial_profile(frames, self.bins, self.nbins, self.sums[b, :n], self.counts[b, :n],
+                               self.profile[b, :n], self.vmin, self.vmax, self.frac_bits, run=self.run, stream=st)
+
+    def _launched(self, b, n, st, meta):
         """keep_results, GPU: the batch's profiles go to PINNED HOST memory by an asynchronous copy on
         the current (consumer) stream, so a long run keeps nothing in HBM (64 frames x 1024 bins =
         256 KiB of host memory per batch).  The kept tensors are valid after :meth:`sync_streams`."""
@@ -683,99 +779,16 @@ class RadialProfileConsumer:
         host.copy_(self.profile[b, :n], non_blocking=True)
         self.results.append((host, meta))
 
-    def _next(self):
-        b = self._b % self._nbuf
-        k = self._b % len(self.streams)
-        self._b += 1
-        return b, self.streams[k]
+    def _reference(self, frames, meta):
+        from .ops import reference
 
-    def process_frames(self, frames, meta):
-        """Integrate ``frames`` (tensors of n elements on this consumer's device, issued on the current
-        stream) that are not queue items -- e.g. frames calibrated on read.  ``meta``: their
-        ``(rank, idx, gevt)``.  GPU: returns the consumer stream the batch runs on."""
-        n = len(frames)
-        if n == 0:
-            return None
-        st = None
-        if self.gpu:
-            b, st = self._next()
-            st.wait_stream(torch.cuda.current_stream(self.device))   # the frames were produced / leased on it
-            with torch.cuda.stream(st):
-                kernels.radial_profile(list(frames), self.bins, self.nbins, self.sums[b, :n], self.counts[b, :n],
-                                       self.profile[b, :n], self.vmin, self.vmax, self.frac_bits, run=self.run,
-                                       stream=st)
-                if self.keep_results:
-                    self._keep(b, n, list(meta))
-        else:
-            from .ops import reference
-
-            s, c, prof = reference.radial_profile_reference(torch.stack([t.reshape(-1) for t in frames]),
-                                                            self._bins_cpu, self.nbins, self.vmin, self.vmax,
-                                                            self.frac_bits)
-            self.run_sum += s.sum(dim=0).numpy()
-            self.run_count += c.to(torch.int64).sum(dim=0).numpy()
-            self.run_frames += n
-            if self.keep_results:
-                self.results.append((prof, list(meta)))
-        self.frames += n
-        return st
-
-    def process(self, items: List[FrameItem]):
-        if not items:
-            return
-        st = self.process_frames([it.data for it in items], [(it.rank, it.idx, it.gevt) for it in items])
-        for it in items:
-            it.release(st) if self.gpu else it.release()
-
-    def poll(self, timeout: float = 0.05, max_items: Optional[int] = None) -> int:
-        """Take up to ``batch`` ready frames (waiting up to ``timeout`` for the first) and process
-        them.  Returns frames processed; raises EndOfStream at the end of the stream."""
-        n_max = self.batch if max_items is None else max(1, min(self.batch, max_items))
-        if not self.gpu:
-            items: List[FrameItem] = []
-            it = self.ep.get(timeout=timeout)
-            if it is None:
-                return 0
-            items.append(it)
-            while len(items) < n_max:
-                try:
-                    nxt = self.ep.get(timeout=0.0)
-                except EndOfStream:
-                    break
-                if nxt is None:
-                    break
-                items.append(nxt)
-            self.process(items)
-            return len(items)
-        # GPU: one native call to lease, one to integrate (clear, kernel, finalize), one to release
-        st = self.streams[self._b % len(self.streams)]
-        slots = self.ep.get_batch(n_max, timeout, st)
-        n = len(slots)
-        if n == 0:
-            return 0
-        C = _ext.load()
-        b, st = self._next()
-        with trace_range("consumer.radial_batch"):
-            C.radial_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, int(self.bins.data_ptr()), self.nbins,
-                           self.vmin, self.vmax, self.frac_bits, int(self.sums[b].data_ptr()),
-                           int(self.counts[b].data_ptr()), int(self.profile[b].data_ptr()), int(self.run.data_ptr()),
-                           int(st.cuda_stream))
-            if self.keep_results:
-                hs = self.ep.pool.headers(slots)
-                with torch.cuda.stream(st):
-                    self._keep(b, n, [(h.rank, h.idx, h.gevt) for h in hs])
-        self.ep.release_batch(slots, st)
-        self.frames += n
-        return n
-
-    def metrics(self) -> dict:
-        return {"frames_consumed": self.frames}
-
-    def sync_streams(self):
-        """Host waits for every batch issued so far (both consumer streams)."""
-        if self.gpu:
-            for st in self.streams:
-                st.synchronize()
+        s, c, prof = reference.radial_profile_reference(torch.stack([t.reshape(-1) for t in frames]), self._bins_cpu,
+                                                        self.nbins, self.vmin, self.vmax, self.frac_bits)
+        self.run_sum += s.sum(dim=0).numpy()
+        self.run_count += c.to(torch.int64).sum(dim=0).numpy()
+        self.run_frames += len(frames)
+        if self.keep_results:
+            self.results.append((prof, list(meta)))
 
     def synchronize(self):
         """Wait for every batch and bring the run accumulator to the host.  Returns
@@ -794,138 +807,73 @@ class RadialProfileConsumer:
         return mean_profile(self.run_sum, self.run_count, self.frac_bits)
 
 
-class DarkStatsConsumer:
+class DarkStatsConsumer(_BatchConsumer):
     """Consumer engine: batches of leased RAW uint16 slots -> K-09 dark statistics (csrc/dark.hip) ->
-    stream-ordered release.  Same surface and stream scheme as :class:`RadialProfileConsumer`.
+    stream-ordered release.
 
     Per run: per-pixel, per-candidate count / sum / sum of squares of the raw ADU inside the window
     ``[adu_lo, adu_hi]`` -- integers, so the result is exact in any frame order.  The kernel owns a
     pixel per launch and uses no atomics, so every consumer stream has its OWN accumulator set (two
-    streams never read-modify-write the same words); :meth:`synchronize` adds the sets on the host.
-    CPU endpoints run the golden model (ops.reference)."""
+    streams never read-modify-write the same words; the buffer row is not used);
+    :meth:`synchronize` adds the sets on the host."""
+
+    name = "dark"
 
     def __init__(self, endpoint: QueueEndpoint, spec, adu_lo: int = 0, adu_hi: Optional[int] = None,
                  batch: Optional[int] = None, stream_kind: str = CONSUMER_STREAM_KIND,
                  streams: int = CONSUMER_STREAMS, ranks_per_gpu: Optional[int] = None):
         from .ops.reference import DARK_MAX_FRAMES
 
-        self.ep = endpoint
         self.spec = spec
         self.kind, self.adu_lo, self.adu_hi = kernels.validate_dark_window(
             spec.kernel_kind, adu_lo, 65535 if adu_hi is None else adu_hi, "dark")
         self.nc = int(spec.n_candidates)
         self.n = int(spec.npix)
-        self.batch = min(resolve_consumer_batch(batch, ranks_per_gpu), kernels.MAX_FRAMES)
-        self.device = endpoint.ring.device
-        self.gpu = self.device.type == "cuda"
         if endpoint.ring.dtype != torch.uint16:
             raise ValueError(f"dark: the queue carries {endpoint.ring.dtype} frames, dark statistics need raw uint16")
         if int(np.prod(endpoint.ring.frame_shape)) != self.n:
             raise ValueError(f"dark: queue frames {tuple(endpoint.ring.frame_shape)} are not the {self.n} pixels "
                              f"of {spec.name}")
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
         self.max_frames = DARK_MAX_FRAMES
-        self.frames = 0
         self.cnt = np.zeros((self.nc, self.n), np.int64)
         self.sum = np.zeros((self.nc, self.n), np.int64)
         self.sq = np.zeros((self.nc, self.n), np.int64)
         if self.gpu:
-            self.streams = _make_streams(self.device, int(streams), stream_kind, owner=self)
-            self.stream = self.streams[0]
             # one accumulator set per stream; set k is only ever touched by launches on stream k
             self._acc = [(torch.zeros((self.nc, self.n), dtype=torch.int32, device=self.device),
                           torch.zeros((self.nc, self.n), dtype=torch.int64, device=self.device),
                           torch.zeros((self.nc, self.n), dtype=torch.int64, device=self.device))
                          for _ in self.streams]
-            self._b = 0
 
     def _check_bound(self, n: int):
         if self.frames + n > self.max_frames:
             raise ValueError(f"dark: {self.frames} + {n} frames would take the run past 2^31 - 1 (the int32 count)")
 
-    def _next(self):
-        k = self._b % len(self.streams)
-        self._b += 1
-        return k, self.streams[k]
+    _check_batch = _check_bound
 
-    def process_frames(self, frames, meta=None):
-        """Add ``frames`` (raw uint16 tensors of n elements on this consumer's device, issued on the
-        current stream) that are not queue items.  GPU: returns the consumer stream the batch runs on."""
-        n = len(frames)
-        if n == 0:
-            return None
-        self._check_bound(n)
-        st = None
-        if self.gpu:
-            k, st = self._next()
-            cnt, s, q = self._acc[k]
-            st.wait_stream(torch.cuda.current_stream(self.device))   # the frames were produced / leased on it
-            with torch.cuda.stream(st):
-                kernels.dark_accumulate(list(frames), self.kind, self.adu_lo, self.adu_hi, cnt, s, q,
-                                        frames_so_far=self.frames, stream=st)
-        else:
-            from .ops import reference
+    def _limit(self, n_max):
+        self._check_bound(1)   # before any lease
+        return max(1, min(n_max, self.max_frames - self.frames))
 
-            c, s, q = reference.dark_accumulate_reference(torch.stack([t.reshape(-1) for t in frames]), self.kind,
-                                                          self.adu_lo, self.adu_hi)
-            self.cnt += c.numpy()
-            self.sum += s.numpy()
-            self.sq += q.numpy()
-        self.frames += n
-        return st
-
-    def process(self, items: List[FrameItem]):
-        if not items:
-            return
-        st = self.process_frames([it.data for it in items])
-        for it in items:
-            it.release(st) if self.gpu else it.release()
-
-    def poll(self, timeout: float = 0.05, max_items: Optional[int] = None) -> int:
-        """Take up to ``batch`` ready frames (waiting up to ``timeout`` for the first) and add them.
-        Returns frames processed; raises EndOfStream at the end of the stream."""
-        n_max = self.batch if max_items is None else max(1, min(self.batch, max_items))
-        n_max = max(1, min(n_max, self.max_frames - self.frames))
-        self._check_bound(1)
-        if not self.gpu:
-            items: List[FrameItem] = []
-            it = self.ep.get(timeout=timeout)
-            if it is None:
-                return 0
-            items.append(it)
-            while len(items) < n_max:
-                try:
-                    nxt = self.ep.get(timeout=0.0)
-                except EndOfStream:
-                    break
-                if nxt is None:
-                    break
-                items.append(nxt)
-            self.process(items)
-            return len(items)
-        # GPU: one native call to lease, one to accumulate, one to release
-        st = self.streams[self._b % len(self.streams)]
-        slots = self.ep.get_batch(n_max, timeout, st)
-        n = len(slots)
-        if n == 0:
-            return 0
-        C = _ext.load()
-        k, st = self._next()
+    def _launch_slots(self, C, slots, b, k, st):
         cnt, s, q = self._acc[k]
-        with trace_range("consumer.dark_batch"):
-            C.dark_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.kind, self.adu_lo, self.adu_hi,
-                         int(cnt.data_ptr()), int(s.data_ptr()), int(q.data_ptr()), int(st.cuda_stream))
-        self.ep.release_batch(slots, st)
-        self.frames += n
-        return n
+        C.dark_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.kind, self.adu_lo, self.adu_hi,
+                     int(cnt.data_ptr()), int(s.data_ptr()), int(q.data_ptr()), int(st.cuda_stream))
 
-    def metrics(self) -> dict:
-        return {"frames_consumed": self.frames}
+    def _launch_tensors(self, frames, b, k, st):
+        cnt, s, q = self._acc[k]
+        kernels.dark_accumulate(frames, self.kind, self.adu_lo, self.adu_hi, cnt, s, q, frames_so_far=self.frames,
+                                stream=st)
 
-    def sync_streams(self):
-        """Host waits for every batch issued so far (all consumer streams)."""
-        if self.gpu:
-            for st in self.streams:
-                st.synchronize()
+    def _reference(self, frames, meta):
+        from .ops import reference
+
+        c, s, q = reference.dark_accumulate_reference(torch.stack([t.reshape(-1) for t in frames]), self.kind,
+                                                      self.adu_lo, self.adu_hi)
+        self.cnt += c.numpy()
+        self.sum += s.numpy()
+        self.sq += q.numpy()
 
     def synchronize(self):
         """Wait for every batch and add the per-stream accumulator sets on the host (exact).  Returns
@@ -949,9 +897,9 @@ class DarkStatsConsumer:
         return DarkStats(self.spec.name, self.kind, self.adu_lo, self.adu_hi, frames, cnt.copy(), s.copy(), q.copy())
 
 
-class SparseFrameConsumer:
+class SparseFrameConsumer(_BatchConsumer):
     """Consumer engine: batches of leased slots -> K-10 zero suppression (csrc/sparse.hip) ->
-    stream-ordered release.  Same surface and stream scheme as :class:`RadialProfileConsumer`.
+    stream-ordered release.
 
     Per frame: the (pixel index, value) pairs with ``thr <= v <= vmax`` (and ``mask != 0``), packed in
     index order; at most ``cap`` per frame (a frame with more stores nothing and is flagged).  With
@@ -961,8 +909,10 @@ class SparseFrameConsumer:
     ``offs[F]`` elements of pix and val; the wait for a batch's header happens after the NEXT batch
     (on the other stream) has been issued.  Finished batches collect in :attr:`results` as
     :class:`psana_ray_amd.sparse.SparseFrames` (``take_results`` hands them over).  Ring slots are
-    released stream-ordered after the scan, not after the copies.  CPU endpoints run the golden
-    model (ops.reference)."""
+    released stream-ordered after the scan, not after the copies."""
+
+    name = "sparse"
+    wants_meta = True
 
     def __init__(self, endpoint: QueueEndpoint, frame_shape, thr: Optional[float] = None, vmax: Optional[float] = None,
                  cap: Optional[int] = None, mask=None, min_peaks: int = 0, peak_params: Optional[PeakFinderParams] = None,
@@ -974,10 +924,9 @@ class SparseFrameConsumer:
         from . import sparse as _sparse
         from .ops.reference import validate_sparse_params
 
-        self.ep = endpoint
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
         self.shape = tuple(int(s) for s in frame_shape)
         self.n = int(np.prod(self.shape))
-        self.batch = min(resolve_consumer_batch(batch, ranks_per_gpu), kernels.MAX_FRAMES)
         if not 1 <= self.n < 2 ** 31:
             raise ValueError("sparse: frames must have 1 .. 2^31 - 1 elements")
         self.thr, self.vmax, self.cap = validate_sparse_params(
@@ -994,8 +943,6 @@ class SparseFrameConsumer:
                 raise ValueError("sparse: peak finder radius must be 1 or 2")
             self._pf_shape = self.shape if len(self.shape) == 3 else (1, *self.shape)
         self.detector, self.layout = str(detector), str(layout)
-        self.device = endpoint.ring.device
-        self.gpu = self.device.type == "cuda"
         if check_ring:
             if endpoint.ring.dtype != torch.float32:
                 raise ValueError(f"sparse: the queue carries {endpoint.ring.dtype} frames, zero suppression needs "
@@ -1009,16 +956,12 @@ class SparseFrameConsumer:
                 raise ValueError(f"sparse: the mask must be uint8 of the frame's shape {self.shape}, got {m.dtype} "
                                  f"{tuple(m.shape)}")
             self._mask_np = np.ascontiguousarray(m.reshape(-1))
-        self.frames = 0
         self.frames_stored = self.frames_skipped = self.frames_overflowed = self.pixels_stored = 0
         self.results = []      # finished batches (SparseFrames), oldest first
         self._pending = collections.deque()   # GPU batches in flight: dicts, oldest first
         self._lock = threading.Lock()
         if self.gpu:
-            self.streams = _make_streams(self.device, int(streams), stream_kind, owner=self)
-            self.stream = self.streams[0]
             B, dev = self.batch, self.device
-            self._nbuf = 2 * len(self.streams)   # buffer k % nbuf is reused by launch k + nbuf, on k's stream
             # header of a batch in ONE row: offs int64 [B + 1] | nnz int32 [B] | flags uint8 [B]
             self._hdr_bytes = 8 * (B + 1) + 4 * B + B
             self._hdr = torch.zeros((self._nbuf, (self._hdr_bytes + 15) // 16 * 16), dtype=torch.uint8, device=dev)
@@ -1029,16 +972,9 @@ class SparseFrameConsumer:
             self._scratch = [torch.empty(kernels.sparsify_scratch_bytes(self.n, self.cap, B), dtype=torch.uint8, device=dev)
                              for _ in self.streams]
             self._mask = None if self._mask_np is None else torch.from_numpy(self._mask_np).to(dev)
+            self._pf = None   # the hit filter's peak finder
             if self.min_peaks > 0:
-                p = self.peak_params
-                self._peaks = torch.empty((self._nbuf, B, p.max_peaks, 8), dtype=torch.float32, device=dev)
-                self._meta = torch.zeros((self._nbuf, 3 * B), dtype=torch.int32, device=dev)
-                self._counts = self._meta[:, :B]
-                self._summary = self._meta[:, B:].view(torch.float32).view(self._nbuf, B, 2)
-                self._pf_scratch = [torch.zeros(kernels.PF_SCRATCH_WORDS, dtype=torch.int32, device=dev)
-                                    for _ in self.streams]
-                self._pf_total = torch.zeros((), dtype=torch.int64, device=dev)
-            self._b = 0
+                self._pf = _PeakBuffers(dev, self.peak_params, self._pf_shape, B, self._nbuf, len(self.streams))
 
     # ------------------------------------------------------------------ buffers
     def _views(self, b: int, n: int):
@@ -1047,12 +983,6 @@ class SparseFrameConsumer:
         row = self._hdr[b]
         return (row[:8 * (B + 1)].view(torch.int64)[:n + 1], row[8 * (B + 1):8 * (B + 1) + 4 * B].view(torch.int32)[:n],
                 row[8 * (B + 1) + 4 * B:self._hdr_bytes][:n])
-
-    def _next(self):
-        b = self._b % self._nbuf
-        k = self._b % len(self.streams)
-        self._b += 1
-        return b, k, self.streams[k]
 
     def _sparse_frames(self, meta, nnz, flags, offs, pix, val):
         from .sparse import SparseFrames
@@ -1085,7 +1015,7 @@ class SparseFrameConsumer:
             self.results.append(sf)
 
     # ------------------------------------------------------------------ the two host steps of a GPU batch
-    def _issued(self, b: int, n: int, st, meta):
+    def _launched(self, b: int, n: int, st, meta):
         """Batch just launched on ``st`` (current stream): header -> pinned host, then advance the older batches."""
         self._hdr_host[b].copy_(self._hdr[b], non_blocking=True)
         ev = torch.cuda.Event()
@@ -1129,103 +1059,51 @@ class SparseFrameConsumer:
         """Sparsify ``frames`` (tensors of n elements on this consumer's device, issued on the current
         stream) that are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank,
         idx, gevt, photon_energy)``.  GPU: returns the consumer stream the batch runs on."""
-        n = len(frames)
-        if n == 0:
-            return None
+        return super().process_frames(frames, [tuple(m) + (None,) * (4 - len(m)) for m in meta])
+
+    def _check_batch(self, n):
         if n > self.batch:
             raise ValueError(f"sparse: {n} frames in a batch of at most {self.batch}")
-        meta = [tuple(m) + (None,) * (4 - len(m)) for m in meta]
-        st = None
-        if self.gpu:
-            b, k, st = self._next()
-            offs, nnz, flags = self._views(b, n)
-            st.wait_stream(torch.cuda.current_stream(self.device))   # the frames were produced / leased on it
-            with torch.cuda.stream(st):
-                fl = [t.reshape(-1) for t in frames]
-                keys = None
-                if self.min_peaks > 0:
-                    keys = self._counts[b, :n]
-                    kernels.peakfind([t.reshape(self._pf_shape) for t in frames], self._pf_shape, self.peak_params,
-                                     self._peaks[b, :n], keys, self._summary[b, :n], st, total=self._pf_total,
-                                     scratch=self._pf_scratch[k])
-                kernels.sparsify(fl, self.thr, self.vmax, self.cap, nnz, flags, offs, self._pix[b], self._val[b],
-                                 mask=self._mask, keys=keys, key_min=self.min_peaks, scratch=self._scratch[k], stream=st)
-                self._issued(b, n, st, meta)
-        else:
-            from .ops import reference
 
-            x = torch.stack([t.reshape(-1) for t in frames])
-            keys = None
-            if self.min_peaks > 0:
-                pk, _ = reference.peakfind_reference(x.reshape(n, *self._pf_shape), self.peak_params)
-                keys = torch.tensor([int(p.shape[0]) for p in pk], dtype=torch.int32)
-            nnz, flags, offs, pix, val = reference.sparsify_reference(x, self.thr, self.vmax, self.cap,
-                                                                      mask=self._mask_np, keys=keys,
-                                                                      key_min=self.min_peaks)
-            self._count(self._sparse_frames(meta, nnz.numpy(), flags.numpy(), offs.numpy(), pix.numpy(), val.numpy()))
-        self.frames += n
-        return st
+    def _meta_of(self, recs):
+        # a slot header carries NaN for "no photon energy", a queue item None
+        return [(r.rank, r.idx, r.gevt, None if r.photon_energy != r.photon_energy else r.photon_energy)
+                for r in recs]
 
-    def process(self, items: List[FrameItem]):
-        if not items:
-            return
-        st = self.process_frames([it.data for it in items],
-                                 [(it.rank, it.idx, it.gevt, it.photon_energy) for it in items])
-        for it in items:
-            it.release(st) if self.gpu else it.release()
+    def _launch_slots(self, C, slots, b, k, st):
+        offs, nnz, flags = self._views(b, len(slots))
+        keys = 0
+        if self._pf is not None:
+            self._pf.launch_slots(C, self.ep, slots, b, k, st)
+            keys = int(self._pf.counts[b].data_ptr())
+        C.sparsify_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.thr, self.vmax, self.cap,
+                         0 if self._mask is None else int(self._mask.data_ptr()), keys, self.min_peaks,
+                         int(nnz.data_ptr()), int(flags.data_ptr()), int(offs.data_ptr()),
+                         int(self._pix[b].data_ptr()), int(self._val[b].data_ptr()),
+                         int(self._scratch[k].data_ptr()), self._scratch[k].numel(), int(st.cuda_stream))
 
-    def poll(self, timeout: float = 0.05, max_items: Optional[int] = None) -> int:
-        """Take up to ``batch`` ready frames (waiting up to ``timeout`` for the first) and process
-        them.  Returns frames processed; raises EndOfStream at the end of the stream."""
-        n_max = self.batch if max_items is None else max(1, min(self.batch, max_items))
-        if not self.gpu:
-            items: List[FrameItem] = []
-            it = self.ep.get(timeout=timeout)
-            if it is None:
-                return 0
-            items.append(it)
-            while len(items) < n_max:
-                try:
-                    nxt = self.ep.get(timeout=0.0)
-                except EndOfStream:
-                    break
-                if nxt is None:
-                    break
-                items.append(nxt)
-            self.process(items)
-            return len(items)
-        # GPU: one native call to lease, one per kernel family (peak finder; clear + scan + pack), one to release
-        st = self.streams[self._b % len(self.streams)]
-        slots = self.ep.get_batch(n_max, timeout, st)
-        n = len(slots)
-        if n == 0:
-            return 0
-        C = _ext.load()
-        b, k, st = self._next()
+    def _launch_tensors(self, frames, b, k, st):
+        n = len(frames)
         offs, nnz, flags = self._views(b, n)
-        sh = int(st.cuda_stream)
-        with trace_range("consumer.sparse_batch"):
-            keys = 0
-            if self.min_peaks > 0:
-                P, H, W = self._pf_shape
-                p = self.peak_params
-                C.peakfind_slots(self.ep.pool, self.ep._slot_bytes, slots, P, H, W, float(p.thr_peak), float(p.son_min),
-                                 int(p.radius), int(p.max_peaks), int(self._peaks[b].data_ptr()),
-                                 int(self._counts[b].data_ptr()), int(self._summary[b].data_ptr()),
-                                 int(self._pf_total.data_ptr()), sh, int(self._pf_scratch[k].data_ptr()))
-                keys = int(self._counts[b].data_ptr())
-            C.sparsify_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.thr, self.vmax, self.cap,
-                             0 if self._mask is None else int(self._mask.data_ptr()), keys, self.min_peaks,
-                             int(nnz.data_ptr()), int(flags.data_ptr()), int(offs.data_ptr()),
-                             int(self._pix[b].data_ptr()), int(self._val[b].data_ptr()),
-                             int(self._scratch[k].data_ptr()), self._scratch[k].numel(), sh)
-        self.ep.release_batch(slots, st)   # after the scan; the copies below read our own buffers
-        hs = self.ep.pool.headers(slots)
-        meta = [(h.rank, h.idx, h.gevt, None if h.photon_energy != h.photon_energy else h.photon_energy) for h in hs]
-        with torch.cuda.stream(st):
-            self._issued(b, n, st, meta)
-        self.frames += n
-        return n
+        keys = None
+        if self._pf is not None:
+            self._pf.launch_tensors(frames, b, k, st)
+            keys = self._pf.counts[b, :n]
+        kernels.sparsify([t.reshape(-1) for t in frames], self.thr, self.vmax, self.cap, nnz, flags, offs, self._pix[b],
+                         self._val[b], mask=self._mask, keys=keys, key_min=self.min_peaks, scratch=self._scratch[k],
+                         stream=st)
+
+    def _reference(self, frames, meta):
+        from .ops import reference
+
+        x = torch.stack([t.reshape(-1) for t in frames])
+        keys = None
+        if self.min_peaks > 0:
+            pk, _ = reference.peakfind_reference(x.reshape(len(frames), *self._pf_shape), self.peak_params)
+            keys = torch.tensor([int(p.shape[0]) for p in pk], dtype=torch.int32)
+        nnz, flags, offs, pix, val = reference.sparsify_reference(x, self.thr, self.vmax, self.cap, mask=self._mask_np,
+                                                                  keys=keys, key_min=self.min_peaks)
+        self._count(self._sparse_frames(meta, nnz.numpy(), flags.numpy(), offs.numpy(), pix.numpy(), val.numpy()))
 
     def take_results(self) -> list:
         """The finished batches collected so far (oldest first); they are removed from :attr:`results`."""
@@ -1237,12 +1115,6 @@ class SparseFrameConsumer:
         return {"frames_consumed": self.frames, "frames_stored": self.frames_stored,
                 "frames_skipped": self.frames_skipped, "frames_overflowed": self.frames_overflowed,
                 "pixels_stored": self.pixels_stored}
-
-    def sync_streams(self):
-        """Host waits for every batch issued so far (both consumer streams)."""
-        if self.gpu:
-            for st in self.streams:
-                st.synchronize()
 
     def synchronize(self):
         """Wait for every batch and collect it.  Returns the list of finished batches not taken yet."""

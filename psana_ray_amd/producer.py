@@ -242,6 +242,8 @@ def main(argv=None) -> int:
     select_copy_engine(args.copy_engine)   # before the HIP runtime initialises
     import torch
 
+    from .consumer import SparseWriter, load_sparse_mask
+    from .models import RadialBinning, make_geometry
     from .models.detector import Mode
     from .parallel.launch import bind_numa_to_device, detect, device_for
     from .pipeline import (DarkStatsConsumer, PeakFinderConsumer, ProducerPipeline, RadialProfileConsumer,
@@ -278,21 +280,17 @@ def main(argv=None) -> int:
                       "or a co-located --consumer_task")
             return 2
         mode = Mode.raw   # frames travel raw; DataReader applies read_mode
-    if args.consumer_task == "radial" and (mode == Mode.raw or int(args.panel_shards) > 1):
-        log.error("--consumer_task radial needs whole calibrated frames (not --mode raw / --panel_shards)")
+    if args.consumer_task in ("radial", "sparse") and (mode == Mode.raw or int(args.panel_shards) > 1):
+        log.error("--consumer_task %s needs whole calibrated frames (not --mode raw / --panel_shards)",
+                  args.consumer_task)
         return 2
     if args.consumer_task == "dark" and (mode != Mode.raw or int(args.panel_shards) > 1):
         log.error("--consumer_task dark needs whole raw frames (--mode raw, no --panel_shards)")
         return 2
-    if args.consumer_task == "sparse" and (mode == Mode.raw or int(args.panel_shards) > 1):
-        log.error("--consumer_task sparse needs whole calibrated frames (not --mode raw / --panel_shards)")
-        return 2
-    if args.out_sparse is not None and args.consumer_task != "sparse":
-        log.error("--out_sparse belongs to --consumer_task sparse")
-        return 2
-    if args.out_dark is not None and args.consumer_task != "dark":
-        log.error("--out_dark belongs to --consumer_task dark")
-        return 2
+    for flag, task in (("out_sparse", "sparse"), ("out_dark", "dark")):
+        if getattr(args, flag) is not None and args.consumer_task != task:
+            log.error("--%s belongs to --consumer_task %s", flag, task)
+            return 2
     shards = int(args.panel_shards)
     if shards > 1:
         from .source.shard import PanelShardSource, shard_layout
@@ -410,16 +408,36 @@ def main(argv=None) -> int:
         if co_consumer:
             # batch: config.pipeline_shape for the ranks sharing this GPU (mpirun -n 4 on fewer GPUs
             # takes the shared-GPU shape, like bench.py)
-            if args.consumer_task == "radial":
-                from .models import RadialBinning, make_geometry
+            # the task, stated once: cons, each() after every poll (or None), finish() -> the result (on the
+            # consumer thread, at the end of the stream), report(result or None, frames consumed) after the join
+            each = None
 
+            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse merge)
+                root, ext = os.path.splitext(path)
+                return path if size == 1 else f"{root}.r{rank}{ext}"
+
+            if args.consumer_task == "radial":
                 geo = getattr(source, "geometry", None) or make_geometry(source.consts.spec)
                 cons = RadialProfileConsumer(ep, RadialBinning.from_geometry(geo, mode, 512))
+                finish = cons.synchronize
+
+                def report(res, consumed):
+                    _, run_count, run_frames = res or (None, np.zeros(1, np.int64), 0)
+                    log.info("Rank %d: co-located consumer processed %d frames, radial accumulator of %d frames, "
+                             "%d pixels", rank, consumed, run_frames, int(run_count.sum()))
             elif args.consumer_task == "dark":
                 cons = DarkStatsConsumer(ep, source.consts.spec)
-            elif args.consumer_task == "sparse":
-                from .consumer import SparseWriter, load_sparse_mask
+                finish = cons.stats
 
+                def report(ds, consumed):
+                    log.info("Rank %d: co-located consumer processed %d frames, dark statistics of %d frames, "
+                             "%d samples", rank, consumed, 0 if ds is None else ds.frames,
+                             0 if ds is None else int(ds.cnt.sum()))
+                    if ds is not None and args.out_dark:
+                        path = rank_path(args.out_dark)
+                        ds.save(path)
+                        log.info("Rank %d: dark statistics written to %s", rank, path)
+            elif args.consumer_task == "sparse":
                 try:
                     smask = load_sparse_mask(args.sparse_mask, frame_shape)
                     cons = SparseFrameConsumer(ep, frame_shape, thr=args.sparse_thr, vmax=args.sparse_vmax,
@@ -428,13 +446,30 @@ def main(argv=None) -> int:
                 except (ValueError, OSError) as e:
                     log.error("--consumer_task sparse: %s", e)
                     return 2
-                spath = args.out_sparse
-                if spath and size > 1:   # one file per rank (they join: python -m psana_ray_amd.sparse merge)
-                    root, ext = os.path.splitext(spath)
-                    spath = f"{root}.r{rank}{ext}"
-                swriter = SparseWriter(spath, args.part_frames)
+                swriter = SparseWriter(args.out_sparse and rank_path(args.out_sparse), args.part_frames)
+
+                def each():
+                    swriter.add(cons.take_results())
+
+                def finish():
+                    cons.synchronize()
+                    each()
+                    swriter.close(cons.empty())
+                    return cons.metrics()
+
+                def report(m, consumed):
+                    m = m or {}
+                    print(f"Consumer {rank} sparse: frames={consumed} stored={m.get('frames_stored', 0)} "
+                          f"skipped={m.get('frames_skipped', 0)} overflowed={m.get('frames_overflowed', 0)} "
+                          f"pixels={m.get('pixels_stored', 0)}", flush=True)
+                    if swriter.paths:
+                        log.info("Rank %d: sparse frames written to %s", rank, ", ".join(swriter.paths))
             else:
                 cons = PeakFinderConsumer(ep, frame_shape, PeakFinderParams())
+                finish = cons.synchronize
+
+                def report(peaks, consumed):
+                    log.info("Rank %d: co-located consumer processed %d frames, %d peaks", rank, consumed, peaks or 0)
             registry.register("consumer", cons.metrics)
 
             def consume():
@@ -443,20 +478,9 @@ def main(argv=None) -> int:
                         cons.poll(timeout=0.1)
                     except EndOfStream:
                         break
-                    if args.consumer_task == "sparse":
-                        swriter.add(cons.take_results())
-                if args.consumer_task == "sparse":
-                    cons.synchronize()
-                    swriter.add(cons.take_results())
-                    swriter.close(cons.empty())
-                    stats["sparse"] = cons.metrics()
-                elif args.consumer_task == "radial":
-                    stats["radial"] = cons.synchronize()
-                elif args.consumer_task == "dark":
-                    stats["dark"] = cons.stats()
-                else:
-                    stats["peaks"] = cons.synchronize()
-                stats["consumed"] = cons.frames
+                    if each is not None:
+                        each()
+                stats.update(result=finish(), consumed=cons.frames)
 
             cons_thread = threading.Thread(target=consume, name="co-consumer", daemon=True)
             cons_thread.start()
@@ -483,31 +507,7 @@ def main(argv=None) -> int:
                          m.get("frames_requeued", 0), m.get("frames_checksummed", 0))
             if cons_thread is not None:
                 cons_thread.join()
-                if args.consumer_task == "radial":
-                    _, run_count, run_frames = stats.get("radial", (None, np.zeros(1, np.int64), 0))
-                    log.info("Rank %d: co-located consumer processed %d frames, radial accumulator of %d frames, "
-                             "%d pixels", rank, stats.get("consumed", 0), run_frames, int(run_count.sum()))
-                elif args.consumer_task == "dark":
-                    ds = stats.get("dark")
-                    log.info("Rank %d: co-located consumer processed %d frames, dark statistics of %d frames, "
-                             "%d samples", rank, stats.get("consumed", 0), 0 if ds is None else ds.frames,
-                             0 if ds is None else int(ds.cnt.sum()))
-                    if ds is not None and args.out_dark:
-                        # one file per rank (they merge exactly: python -m psana_ray_amd.dark merge)
-                        root, ext = os.path.splitext(args.out_dark)
-                        path = args.out_dark if size == 1 else f"{root}.r{rank}{ext}"
-                        ds.save(path)
-                        log.info("Rank %d: dark statistics written to %s", rank, path)
-                elif args.consumer_task == "sparse":
-                    m = stats.get("sparse", {})
-                    print(f"Consumer {rank} sparse: frames={stats.get('consumed', 0)} stored={m.get('frames_stored', 0)} "
-                          f"skipped={m.get('frames_skipped', 0)} overflowed={m.get('frames_overflowed', 0)} "
-                          f"pixels={m.get('pixels_stored', 0)}", flush=True)
-                    if swriter.paths:
-                        log.info("Rank %d: sparse frames written to %s", rank, ", ".join(swriter.paths))
-                else:
-                    log.info("Rank %d: co-located consumer processed %d frames, %d peaks", rank,
-                             stats.get("consumed", 0), stats.get("peaks", 0))
+                report(stats.get("result"), stats.get("consumed", 0))
         finally:
             reporter.stop(final_sample=args.metrics_interval > 0 or args.metrics_json is not None)
         return rc
