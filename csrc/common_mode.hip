@@ -41,45 +41,13 @@
 
 #include <algorithm>
 
-// Workgroups of the epix10k2M kernel per CU (LDS sizing).  4: the kernel alone fills the CU; 3: a
-// quarter of every CU's LDS and VGPRs stays free, so the consumer's peak finder can run BESIDE the
-// producer's common mode on the same CUs (device-resident pipeline).
-// Frames per workgroup of the epix10k2M kernel.  2 = frame k+1's raw words prefetched during frame
-// k's medians (3 workgroups per CU, 168 VGPRs): measured equal to 1 on the same MI355X (6.59-6.60
-// vs 6.59-6.61 us/frame, device-resident pipeline 118.9k vs 118.4k fr/s on that box,
-// tools/gpu_cm_ab.sh), so the simpler single-frame form ships.
-#ifndef PR_CM_FPW
-#define PR_CM_FPW 1
-#endif
-#ifndef PR_CM_GPRE
-#define PR_CM_GPRE 0
-#endif
-// Raw-word loads of the compile-time (production) kernels: 1 = non-temporal (stream cache policy),
-// 0 = plain.  (The read-ceiling probe at four workgroups per CU read 5.00 TB/s non-temporal vs 6.03
-// plain, profiles/r2/pf/read_ceiling.md.)
-#ifndef PR_CM_RAW_NT
-#define PR_CM_RAW_NT 1
-#endif
-// Output stores of the production kernels: 0 = plain; 1 = non-temporal (streaming) for calib-mode
-// frames; 2 = non-temporal for the image placement too; 3 = calib-mode frames non-temporal for the
-// 128-B lines a tile row owns, plain for the lines it shares with its neighbour tile (cm_flush).  Same-box A/B, device-resident pipeline
-// (common mode + peak finder), two boxes (profiles/r4/cm_pass1, cm_pass2): level 1 calib 144.6k /
-// 145.0k / 144.9k / 143.6k vs plain 140.6k / 141.3k / 141.2k / 139.8k fr/s (+2.7 %), image mode
-// unchanged; level 2 costs image mode 13 % (100.9k vs 115.8k: partial-line image runs).  Kernel
-// alone: memory phases 4.14 vs 4.26 us/frame, full kernel within 0.5 %.
-#ifndef PR_CM_NT_STORE
-#define PR_CM_NT_STORE 1
-#endif
-// Threads per workgroup of the epix10k2M production kernel (4 or 6 waves; the tile and four
-// workgroups per CU are unchanged: 6 waves leave each wave 80 VGPRs)
-#ifndef PR_CM_EPIX_BLOCK
-#define PR_CM_EPIX_BLOCK 256
-#endif
-#ifndef PR_CM_EPIX_WG_PER_CU
-#define PR_CM_EPIX_WG_PER_CU ((PR_CM_FPW > 1 || PR_CM_GPRE) ? 3 : 4)
-#endif
-
 namespace pr {
+
+// epix10k2M production kernel: 256 threads (4 waves) per workgroup, four workgroups per CU -- the
+// kernel alone fills the CU's LDS and VGPRs; three per CU (room for a co-resident consumer kernel)
+// measured the same or slower (profiles/r3/cm/cm_kernel_r3.md, profiles/r5/README.md).
+constexpr int kEpixBlock = 256;
+constexpr int kEpixWgPerCu = 4;
 
 // ---- phase stamps (diagnostic build only: -DPR_CM_STAMPS=1, tools/cm_stamps.py) ----------------
 // Every wave of the epix10k2M production kernel records the shader clock at its phase boundaries
@@ -397,15 +365,12 @@ __device__ __forceinline__ void cm_decode8(const uint4 rw, const uint32_t ep, co
   }
 }
 
-// PR_CM_BASE_FAST = 1: wave-uniform fast paths for items in which no pixel of the whole wave left the
-// first candidate table (no gain switch: epix10ka bit 14 / Jungfrau bits 14-15 clear everywhere) --
+// Base-table fast paths (profiles/r5/README.md section 4, ab5/): wave-uniform paths for items in
+// which no pixel of the whole wave left the first candidate table (no gain switch: epix10ka bit 14 / Jungfrau bits 14-15 clear everywhere) --
 // in the decode (v = ADU - table-0 pedestal, no per-pixel mask / select, no candidate bits) and in
 // the store phase (table-0 gain factor, no per-pixel select).  Gain switching marks bright pixels
 // only (synthetic epix10k2M: 2e-5 of the 8-pixel groups), so nearly every item takes them; a wave
 // that meets one switched pixel runs the general path for that item.
-#ifndef PR_CM_BASE_FAST
-#define PR_CM_BASE_FAST 1
-#endif
 template <int KIND>
 __device__ __forceinline__ bool cm_base_only(const uint4 rw) {
   const uint32_t b = rw.x | rw.y | rw.z | rw.w;
@@ -474,9 +439,6 @@ __device__ __forceinline__ uint32_t cm_need(uint32_t cbits) {
   else return 1u | ((cbits & 0x5555u) ? 2u : 0u) | ((cbits & 0xAAAAu) ? 4u : 0u);
 }
 
-#ifndef PR_CM_UNDEF_TABLES
-#define PR_CM_UNDEF_TABLES 1
-#endif
 // A table the group does not need (no pixel selects that candidate) is left UNDEFINED, not zeroed:
 // every consumer selects it only for pixels of that candidate (v_bfi on the candidate bits), and a
 // zero fill costs 8 v_mov per group (phase 1 and phase 3: 80 VALU per lane of the production kernel).
@@ -490,27 +452,17 @@ __device__ __forceinline__ void load8(const float* __restrict__ t, int64_t npix,
       u = *reinterpret_cast<const f32x4_t*>(t + k * npix + pix);
       w = *reinterpret_cast<const f32x4_t*>(t + k * npix + pix + 4);
     } else {   // an empty asm "defines" the registers: no instruction (freeze(undef) would be a v_mov 0)
-#if PR_CM_UNDEF_TABLES
       asm("" : "=v"(u));
       asm("" : "=v"(w));
-#else
-      u = f32x4_t{0.f, 0.f, 0.f, 0.f};
-      w = u;
-#endif
     }
     a[k][0] = u.x; a[k][1] = u.y; a[k][2] = u.z; a[k][3] = u.w;
     a[k][4] = w.x; a[k][5] = w.y; a[k][6] = w.z; a[k][7] = w.w;
   }
 }
 
-// PR_CM_OFF32: the production kernel's per-item loads address a per-frame uniform global base (SGPR)
+// The production kernel's per-item loads and stores address a per-frame uniform global base (SGPR)
 // plus a 32-bit element offset within the tile, instead of a 64-bit per-item pointer (64-bit VALU
-// adds per load; generic-pointer flat loads for the tables).  Same-box A/B (profiles/r4/off32/):
-// kernel 5.39-5.43 vs 5.48-5.50 us/frame (flags 0: 4.05-4.07 vs 4.15-4.17), 120 -> 109 VGPRs,
-// device-resident pipeline 151.0-153.8k vs 149.2-151.7k.
-#ifndef PR_CM_OFF32
-#define PR_CM_OFF32 1
-#endif
+// adds per access; generic-pointer flat loads for the tables): profiles/r4/README.md section 8.
 // tables[k] = base of candidate table k at the tile origin (uniform); o = element offset in the tile
 template <int NT>
 __device__ __forceinline__ void load8o(const PR_GLOBAL float* const (&tb)[NT], uint32_t o, uint32_t need,
@@ -575,42 +527,21 @@ __device__ __forceinline__ float cm_gain(const float (&ga)[NT][8], uint32_t cb, 
 // cost a v_mov per pixel in a VALU-bound kernel).  That relies on LLVM keeping
 // amdgcn.fmed3(x, s, x) as a med3 and not folding it to x, which
 // tests/test_med3_fill_isa.py checks on the compiled gfx950 code (v_med3_f32 vA, vX, vS, vX
-// present) and the bitwise GPU tests check numerically; PR_CM_MED3_FILL=0 builds the compare +
-// select reference.
-#ifndef PR_CM_MED3_FILL
-#define PR_CM_MED3_FILL 1
-#endif
+// present) and the bitwise GPU tests check numerically (profiles/r5/README.md section 4, ab4/).
 __device__ __forceinline__ float nan_fill(float x, float s) {
-#if PR_CM_MED3_FILL
   return __builtin_amdgcn_fmed3f(x, s, x);
-#else
-  return x != x ? s : x;
-#endif
 }
 
 // Store-phase output of one 8-pixel group.  NaN tile entries are pixels that were not CM-eligible:
 // their raw value comes from the group's side slot (or, on slot overflow, is recomputed from raw
 // + pedestal in global memory); masked pixels have a zero gain factor, Jungfrau's invalid gain
 // code a zero value, so both come out 0.
-// PR_CM_LDS_PROBE = 1 (diagnostic, WRONG results): the store phase's tile reads and the flush's reads
-// use bank-conflict-free addresses instead of the tile layout's -- the timing bound of removing the
-// memory phases' LDS read conflicts (tools/lds_bank_model.py attributes all 660 conflict cycles per
-// tile to those phases: phase-1 / phase-3 b128 writes 176 + 176, phase-3 b128 reads 176, flush 132).
-#ifndef PR_CM_LDS_PROBE
-#define PR_CM_LDS_PROBE 0
-#endif
 template <int KIND, int NT, bool BASE = false, bool SG = false>
 __device__ __forceinline__ void cm_out8(const float* tile_row, const float* side, uint32_t cb, uint32_t slot,
                                         const float (&ga)[NT][8], const PR_GLOBAL uint16_t* raw,
                                         const float* __restrict__ ped, int64_t npix, int64_t pix, float (&o)[8]) {
-#if PR_CM_LDS_PROBE
-  tile_row = side - 8 * 1024 + 4 * (int)threadIdx.x;   // the tile base is side - R * P; 4 dwords per lane
-  const float4 t0 = *reinterpret_cast<const float4*>(tile_row);
-  const float4 t1 = *reinterpret_cast<const float4*>(tile_row + 1024);
-#else
   const float4 t0 = *reinterpret_cast<const float4*>(tile_row);
   const float4 t1 = *reinterpret_cast<const float4*>(tile_row + 4);
-#endif
   float xv[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
   if (slot < kSideOverflow) {
     const float4 s0 = *reinterpret_cast<const float4*>(side + 8 * slot);
@@ -638,9 +569,12 @@ __device__ __forceinline__ void cm_out8(const float* tile_row, const float* side
 // no loads in this loop every store is fire-and-forget (the round-1 form that interleaved the
 // gain-factor loads with the stores serialised one store round trip per 8-pixel group).
 // Frame layout: 16 B per lane, consecutive lanes along tile rows.
+// LEVEL 1 (calib-mode frames): streaming (non-temporal) stores, +2.7 % on the device-resident
+// pipeline; LEVEL 2 (image placement): plain, streaming the partial-line image runs costs 13 %
+// (profiles/r4/README.md, cm_pass1 / cm_pass2).
 template <int LEVEL>
 __device__ __forceinline__ void st_out4(PR_GLOBAL float4* p, const float4 v) {
-  if constexpr (LEVEL == 1 ? PR_CM_NT_STORE >= 1 : PR_CM_NT_STORE == 2) {
+  if constexpr (LEVEL == 1) {
     f32x4_t x;
     x.x = v.x; x.y = v.y; x.z = v.z; x.w = v.w;
     __builtin_nontemporal_store(x, (PR_GLOBAL f32x4_t*)p);
@@ -649,8 +583,7 @@ __device__ __forceinline__ void st_out4(PR_GLOBAL float4* p, const float4 v) {
   }
 }
 
-// Flush of the float4 chunks [j0, j0 + nj) of every tile row; NT: streaming (non-temporal) stores.
-template <bool NT>
+// Flush of the float4 chunks [j0, j0 + nj) of every tile row with plain stores.
 __device__ __forceinline__ void cm_flush_cols(const float* tile, int P, int R, PR_GLOBAL float* ob, int panel_cols,
                                               int j0, int nj) {
   if (nj <= 0) return;
@@ -660,8 +593,7 @@ __device__ __forceinline__ void cm_flush_cols(const float* tile, int P, int R, P
   for (int e = threadIdx.x; e < R * nj; e += blockDim.x) {
     const float4 v = *reinterpret_cast<const float4*>(tile + r * P + 4 * (j0 + j));
     PR_GLOBAL float4* d = (PR_GLOBAL float4*)(ob + (uint32_t)(r * panel_cols + 4 * (j0 + j)));
-    if constexpr (NT) st_out4<1>(d, v);
-    else st_f4(d, v);
+    st_f4(d, v);
     r += dr;
     j += dj;
     if (j >= nj) {
@@ -671,49 +603,23 @@ __device__ __forceinline__ void cm_flush_cols(const float* tile, int P, int R, P
   }
 }
 
-// PR_CM_NT_STORE = 3 (calib mode): non-temporal stores for the 128-B lines a tile row owns whole, plain
-// stores for the lines it shares with its neighbour tile (a 48-float stripe row is 192 B: every other
-// line is half this tile's, half the next one's).  A streaming store evicts its partial line before the
-// neighbour's half arrives, so the L2 writes it back twice: +9 % WRITE_SIZE per frame with every store
-// non-temporal (profiles/r5/README.md); the neighbour tile of the same frame runs on the same XCD
-// (table-major order, 64 frames per launch), so a plain store's half line waits in L2 for its partner.
+// Calib-mode flush of the whole tile: every store streaming.  (Plain stores for the 128-B lines a tile
+// row shares with its neighbour tile write exactly the payload but cost 1.7 % kernel time,
+// profiles/r5/README.md section 3.)
 __device__ __forceinline__ void cm_flush(const float* tile, int P, int R, int C, PR_GLOBAL float* out, int64_t base,
                                          int panel_cols, bool nt = true) {
   const int C4 = C >> 2;
   if (!nt) {   // plain stores (a frame for another process's ring), workgroup-uniform
-    cm_flush_cols<false>(tile, P, R, out + base, panel_cols, 0, C4);
+    cm_flush_cols(tile, P, R, out + base, panel_cols, 0, C4);
     return;
   }
-#if PR_CM_NT_STORE == 3 && !PR_CM_LDS_PROBE
-  if ((panel_cols & 31) == 0) {   // every tile row starts at the same offset within its 128-B line
-    PR_GLOBAL float* const ob = out + base;
-    const int s = (int)(reinterpret_cast<uintptr_t>(ob) & 127);        // byte offset of the rows in their lines
-    const int jlo = min(C4, ((128 - s) & 127) >> 4);                    // first chunk of a whole line
-    const int jhi = max(jlo, (((s + 16 * C4) & ~127) - s) >> 4);        // end of the last whole line
-    cm_flush_cols<true>(tile, P, R, ob, panel_cols, jlo, jhi - jlo);
-    cm_flush_cols<false>(tile, P, R, ob, panel_cols, 0, jlo);
-    cm_flush_cols<false>(tile, P, R, ob, panel_cols, jhi, C4 - jhi);
-    return;
-  }
-#endif
-#ifndef PR_CM_FLUSH32
-#define PR_CM_FLUSH32 PR_CM_OFF32
-#endif
-#if PR_CM_FLUSH32
   PR_GLOBAL float* const ob = out + base;   // uniform tile origin; 32-bit offsets per store
   // (row, float4 column) of element e advance incrementally by blockDim.x elements per iteration:
   // one integer division per thread instead of one per element
   const int dr = (int)blockDim.x / C4, dj = (int)blockDim.x - dr * C4;
   int r = (int)threadIdx.x / C4, j = (int)threadIdx.x - r * C4;
   for (int e = threadIdx.x; e < R * C4; e += blockDim.x) {
-#if PR_CM_LDS_PROBE
-    const float4 v = *reinterpret_cast<const float4*>(tile + 4 * e);
-#else
     const float4 v = *reinterpret_cast<const float4*>(tile + r * P + 4 * j);
-#endif
-#if PR_CM_MEMPROBE & 8
-    if (__float_as_uint(v.x) == 0x7fc01234u)   // never: the flush's LDS reads and loop stay, the stores go
-#endif
     st_out4<1>((PR_GLOBAL float4*)(ob + (uint32_t)(r * panel_cols + 4 * j)), v);
     r += dr;
     j += dj;
@@ -722,13 +628,6 @@ __device__ __forceinline__ void cm_flush(const float* tile, int P, int R, int C,
       ++r;
     }
   }
-#else
-  for (int e = threadIdx.x; e < R * C4; e += blockDim.x) {
-    const int r = e / C4, j = e - r * C4;
-    const float4 v = *reinterpret_cast<const float4*>(tile + r * P + 4 * j);
-    st_out4<1>((PR_GLOBAL float4*)(out + base + (int64_t)r * panel_cols + 4 * j), v);
-  }
-#endif
 }
 
 // Image layout (fused K-05): every panel sits in the image by an integer rotation + translation,
@@ -770,59 +669,18 @@ __device__ __forceinline__ void cm_fill_gaps(const ImgOut& io, const GapPre& g, 
     cm_gap_store(out, io.gaps[e]);   // shares beyond kGapPre entries per thread (not the production shapes)
 }
 
-// PR_CM_PLACEPROBE (diagnostic, WRONG results): bit 1 drops the ragged 4-B stores, bit 2 the
-// full-chunk stores of row-run panels, bit 4 those of column-run panels (the LDS reads stay).
-#ifndef PR_CM_PLACEPROBE
-#define PR_CM_PLACEPROBE 0
-#endif
-#ifndef PR_CM_PLACE_CQ
-#define PR_CM_PLACE_CQ 4
-#endif
-#define PR_PLACE_KEEP(bit, v) (!(PR_CM_PLACEPROBE & (bit)) || __float_as_uint((v)) == 0x7fc01234u)
-// PR_CM_IMG_NT (bit 1 = row-run panels, bit 2 = column-run panels; shipped 3 with PR_CM_PLACE_LA):
-// image placement stores streaming (non-temporal) for the 128-B
-// lines that lie wholly inside one image run, plain for the lines a run shares with a gap or a
-// neighbour tile (the image form of PR_CM_NT_STORE 3; all-streaming placement stores cost 13 %).
-// With the round-5 column walk (a wave: 4 chunks x 16 runs) it LOST: kernel (--mode image --no-gaps,
-// flags 3) 5.78-5.80 vs 5.37-5.39 us/frame, image pipeline 125.2-126.5k vs 136.2-137.7k fr/s
-// (profiles/r6/image/); split by panel kind (profiles/r6/image_ntrc/) row-run panels only 5.34-5.37
-// (neutral), column-run panels only 5.88-5.97: every line arrived as two half-line streaming writes
-// from two instructions.  With the line-aligned column walk (PR_CM_PLACE_LA: each store instruction
-// writes 8 whole lines) it WINS: flags 0 4.60-4.64 vs 5.05-5.08, flags 3 5.32 vs 5.38-5.40, image
-// pipeline 142.8-146.8k vs 136.0-137.8k (profiles/r6/image_la/; line-aligned alone: neutral).
-#ifndef PR_CM_IMG_NT
-#define PR_CM_IMG_NT 3
-#endif
-// PR_CM_IMG_T = 1 (A/B, not kept): column-run panels read each image chunk's four tile elements as
-// one ds_read_b128 of a tile ROW per lane and transpose 4x4 blocks in the quad with DPP (VERDICT r5
-// next #3: one LDS read per 16-B store instead of four ds_read_b32).  Bitwise (45 CM / image tests);
-// same box, 3 rounds: kernel (--mode image --no-gaps, flags 3) 5.44 / 5.44 / 5.46 vs 5.38 / 5.40 /
-// 5.40 us/frame, image pipeline 135.5k / 136.9k / 136.6k vs 139.9k / 137.8k / 136.4k fr/s
-// (profiles/r6/image_t/): the LDS reads are not what the placement waits on (cf. r5 sections 14, 19).
-#ifndef PR_CM_IMG_T
-#define PR_CM_IMG_T 0
-#endif
-// Column-run panels, line-aligned walk (see cm_place); 0 = the round-5 walk (PR_CM_PLACE_CQ chunks
-// x 64 / CQ runs per wave, lines split between instructions)
-#ifndef PR_CM_PLACE_LA
-#define PR_CM_PLACE_LA 1
-#endif
-// quad_perm exchange with bound_ctrl (no `old` operand to materialise)
-template <int CTRL>
-__device__ __forceinline__ float quad_x(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-template <int NTMASK = 3>
+// Image placement store: streaming (non-temporal) for the 128-B lines that lie wholly inside one
+// image run, plain for the lines a run shares with a gap or a neighbour tile (all-streaming placement
+// stores cost 13 %).  It pays because every store instruction of cm_place's walks writes whole lines
+// (profiles/r6/README.md, image_la/).
 __device__ __forceinline__ void st_img4(PR_GLOBAL float* out, int32_t e, int32_t run_lo, int len, const float4 v,
                                         bool nt) {
-#if PR_CM_IMG_NT
-  if ((PR_CM_IMG_NT & NTMASK) && nt && (e & ~31) >= run_lo && (e | 31) < run_lo + len) {
+  if (nt && (e & ~31) >= run_lo && (e | 31) < run_lo + len) {
     f32x4_t x;
     x.x = v.x; x.y = v.y; x.z = v.z; x.w = v.w;
     __builtin_nontemporal_store(x, (PR_GLOBAL f32x4_t*)(out + e));
     return;
   }
-#endif
   st_out4<2>((PR_GLOBAL float4*)(out + e), v);
 }
 // nt = false: plain stores only (a frame for another process's ring, as cm_flush)
@@ -858,10 +716,8 @@ __device__ __forceinline__ void cm_place(const float* tile, int P, int R, int C,
   const int di = step > 0 ? ie : -ie;
   auto tile_at = [&](int run, int t) { return tile + run * rb_step + (step > 0 ? t : len - 1 - t) * ie; };
   // lanes -> (run, full chunk): rows-case runs are tile rows (contiguous in LDS too), so consecutive
-  // lanes take consecutive chunks of one run; column-case runs are tile columns, so a wave takes 4
-  // chunks (64 B of image) of 16 neighbouring columns -- LDS reads 2-way instead of 32-way
-  // bank-conflicted, global stores 16 segments of 64 B.  The (run, chunk) walk is incremental (one
-  // integer division per thread, not per chunk).
+  // lanes take consecutive chunks of one run, walked incrementally (one integer division per
+  // thread, not per chunk); column-case runs are tile columns, walked line-aligned (below).
   // One loop per layout (no per-item selects on the uniform `rows`), tile and image addresses
   // linear in (run, chunk) with the direction folded into a signed stride, 32-bit image offsets
   // (the image is < 2^31 elements; Geometry.panel_placement): 6.85-6.91 vs 7.04-7.07 us/frame for
@@ -877,7 +733,7 @@ __device__ __forceinline__ void cm_place(const float* tile, int P, int R, int C,
       for (; run < nruns;) {
         const float* tp = tb + run * P + 4 * k * di;
         const float4 v4 = make_float4(tp[0], tp[di], tp[2 * di], tp[3 * di]);
-        if (PR_PLACE_KEEP(2, v4.x)) st_img4<1>(out, ob + run * oo + 4 * k, (int32_t)lo + run * oo, len, v4, nt);
+        st_img4(out, ob + run * oo + 4 * k, (int32_t)lo + run * oo, len, v4, nt);
         run += drun;
         k += dk;
         if (k >= nfull) {
@@ -885,7 +741,7 @@ __device__ __forceinline__ void cm_place(const float* tile, int P, int R, int C,
           ++run;
         }
       }
-    } else if (PR_CM_PLACE_LA) {
+    } else {
       // line-aligned: a wave takes 8 runs x one 128-B image line each (lane = run offset x chunk of
       // the line), so a store instruction writes 8 whole lines instead of 16 half lines (the runs'
       // line phases differ: each lane locates its chunk from its run's own phase)
@@ -899,52 +755,7 @@ __device__ __forceinline__ void cm_place(const float* tile, int P, int R, int C,
         if (run < nruns && k >= 0 && k < nfull) {
           const float* tp = tb + run + 4 * k * di;
           const float4 v4 = make_float4(tp[0], tp[di], tp[2 * di], tp[3 * di]);
-          st_img4<2>(out, a0 + 4 * k, (int32_t)lo + run * oo, len, v4, nt);
-        }
-      }
-    } else if (PR_CM_IMG_T && (nruns & 3) == 0) {
-      // quad transpose: lane q of a quad reads tile row (position t_lo + 4k + q) of 4 neighbouring
-      // columns as ONE ds_read_b128, the quad transposes the 4x4 block with DPP exchanges, and lane q
-      // stores chunk k of column c0 + q.  A wave takes 4 chunks x 16 columns (the shipped CQ 4 shape).
-      const int q = (int)threadIdx.x & 3, quad = ((int)threadIdx.x & 63) >> 2;
-      const int nq = (nfull + 3) >> 2, ncg = (nruns + 15) >> 4, nw = nb >> 6;
-      for (int u = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6); u < ncg * nq; u += nw) {
-        const int g = u / nq, a = u - g * nq;
-        const int c0 = 16 * g + 4 * (quad & 3), k = 4 * a + (quad >> 2);
-        const bool ok = c0 < nruns && k < nfull;          // uniform over the quad
-        const int tq = t_lo + 4 * (ok ? k : 0) + q;
-        const int r = step > 0 ? tq : len - 1 - tq;
-        const float4 m = *reinterpret_cast<const float4*>(tile + r * P + (ok ? c0 : 0));
-        // (every exchange runs on all four lanes: the opaque asm keeps the compiler from sinking a
-        // DPP read into the lane-divergent select, where it would read a disabled partner)
-        const bool odd = q & 1, hi = q & 2;
-        float p0 = quad_x<0xB1>(m.x), p1 = quad_x<0xB1>(m.y), p2 = quad_x<0xB1>(m.z), p3 = quad_x<0xB1>(m.w);
-        asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3));
-        const float y0 = odd ? p1 : m.x, y1 = odd ? m.y : p0, y2 = odd ? p3 : m.z, y3 = odd ? m.w : p2;
-        float s0 = quad_x<0x4E>(y0), s1 = quad_x<0x4E>(y1), s2 = quad_x<0x4E>(y2), s3 = quad_x<0x4E>(y3);
-        asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3));
-        const float z0 = hi ? s2 : y0, z1 = hi ? s3 : y1, z2 = hi ? y2 : s0, z3 = hi ? y3 : s1;
-        if (ok) st_img4(out, ob + (c0 + q) * oo + 4 * k, (int32_t)lo + (c0 + q) * oo, len, make_float4(z0, z1, z2, z3), nt);
-      }
-    } else {
-      // a wave takes PR_CM_PLACE_CQ chunks (16 B each) of 64 / PR_CM_PLACE_CQ neighbouring columns
-      // (see the general form)
-      constexpr int CQ = PR_CM_PLACE_CQ;
-      const int per = CQ * nruns, nq = (nfull + CQ - 1) / CQ;
-      int a = (int)threadIdx.x / per, w = (int)threadIdx.x - a * per;
-      const int da = nb / per, dw = nb - da * per;
-      for (; a < nq;) {
-        const int run = w / CQ, k = CQ * a + (w % CQ);
-        if (k < nfull) {
-          const float* tp = tb + run + 4 * k * di;
-          const float4 v4 = make_float4(tp[0], tp[di], tp[2 * di], tp[3 * di]);
-          if (PR_PLACE_KEEP(4, v4.x)) st_img4<2>(out, ob + run * oo + 4 * k, (int32_t)lo + run * oo, len, v4, nt);
-        }
-        a += da;
-        w += dw;
-        if (w >= per) {
-          w -= per;
-          ++a;
+          st_img4(out, a0 + 4 * k, (int32_t)lo + run * oo, len, v4, nt);
         }
       }
     }
@@ -956,7 +767,7 @@ __device__ __forceinline__ void cm_place(const float* tile, int P, int R, int C,
       const int run = e / n_rag, j = e - run * n_rag;
       const int t = j < n_head ? j : t_hi + (j - n_head);
       const float v1 = *tile_at(run, t);
-      if (PR_PLACE_KEEP(1, v1)) out[lo + (int64_t)run * outer + t] = v1;
+      out[lo + (int64_t)run * outer + t] = v1;
     }
   }
 }
@@ -1020,24 +831,12 @@ struct TileCoord {
 // off; an XCD-grouping remap of the table-major order changed nothing, 4.75 vs 4.65, and an
 // XCD-local frame-major order lost, 5.29 vs 4.90.)
 // With tg.fpw > 1 a workgroup takes fpw consecutive frames of its tile (t.f = the first).
-// Image layout (desc != null, PR_CM_IMG_ORDER): in a panel whose tile COLUMNS are image rows (90 / 270
-// degree placements) the tile that continues an image row is the next ASIC row, so those panels
-// number their tiles ASIC-row fastest: the two tiles sharing the 128-B lines at a run's ends then run
-// 64 workgroups apart on the same XCD (as row-run panels' neighbours do) instead of 64 x ASICs per
-// row, and the L2 merges the halves before a partial line is written back.
-#ifndef PR_CM_IMG_ORDER
-#define PR_CM_IMG_ORDER 0
-#endif
-// XCD-grouped order for launches of at most PR_CM_XCD_MAX_FRAMES frames (TileGeom.xcd_map): with few
+// XCD-grouped order for launches of at most kXcdMaxFrames frames (TileGeom.xcd_map): with few
 // frames per launch a tile's constant tables are re-read per frame group on every XCD and dominate
-// the traffic (Jungfrau-16M, 8-frame chunks: 43.4 -> 37.7 us/frame; epix10k2M at 8 frames 6.35 ->
-// 5.76), while at 32-64 frames the plain table-major order spreads the raw / output streams better
-// (epix10k2M 64 frames: 4.59 vs 4.72), profiles/r5/README.md section 20
-#ifndef PR_CM_XCD_MAX_FRAMES
-#define PR_CM_XCD_MAX_FRAMES 12
-#endif
-__device__ __forceinline__ TileCoord cm_coords(const TileGeom& tg, int R, int C, const int id = (int)blockIdx.x,
-                                               const int32_t* desc = nullptr) {
+// the traffic, while at 32-64 frames the plain table-major order spreads the raw / output streams
+// better (profiles/r5/README.md section 20)
+constexpr int kXcdMaxFrames = 12;
+__device__ __forceinline__ TileCoord cm_coords(const TileGeom& tg, int R, int C, const int id = (int)blockIdx.x) {
   TileCoord t;
   const int ng = (tg.nframes + tg.fpw - 1) / tg.fpw;
   const int per_panel = tg.asics_per_col * tg.asics_per_row;
@@ -1056,13 +855,6 @@ __device__ __forceinline__ TileCoord cm_coords(const TileGeom& tg, int R, int C,
   t.panel = tile / per_panel;
   t.ar = (tile % per_panel) / tg.asics_per_row;
   t.ac = (tile % per_panel) % tg.asics_per_row;
-  if (PR_CM_IMG_ORDER && desc != nullptr) {
-    const int sx = desc[3 * t.panel + 2];
-    if (sx != 1 && sx != -1) {   // column runs: ASIC rows fastest
-      t.ar = (tile % per_panel) % tg.asics_per_col;
-      t.ac = (tile % per_panel) / tg.asics_per_col;
-    }
-  }
   t.base = (int64_t)t.panel * tg.panel_rows * tg.panel_cols + (int64_t)t.ar * R * tg.panel_cols + (int64_t)t.ac * C;
   return t;
 }
@@ -1215,15 +1007,11 @@ __device__ __forceinline__ int dpp_quad_i(int x) {
 // carry neither a NaN nor a sign of zero that matters (a -0 median subtracts like +0).  The s_nop
 // covers the VALU-write -> DPP-read hazard (2 wait states), which the compiler does not insert for
 // inline asm.  PERM: 0xB1 = quad_perm [1,0,3,2] (lane q^1), 0x1B = [3,2,1,0] (lane q^3).
-#ifndef PR_CM_DPP_MAX
-#define PR_CM_DPP_MAX 1
-#endif
 #define PR_DPP_MAX_ASM(PERMSTR, SA, SB) \
   asm("s_nop 1\n\tv_max_f32_dpp %0, " SA "%1, " SB "%2 quad_perm:" PERMSTR " row_mask:0xf bank_mask:0xf" \
       : "=v"(r) : "v"(a), "v"(b))
 template <int PERM, bool NEG_A, bool NEG_B>
 __device__ __forceinline__ float max_dpp(float a, float b) {
-#if PR_CM_DPP_MAX
   static_assert(PERM == 0xB1 || PERM == 0x1B, "max_dpp: quad permutation");
   float r;
   if constexpr (PERM == 0xB1) {
@@ -1238,10 +1026,6 @@ __device__ __forceinline__ float max_dpp(float a, float b) {
     else PR_DPP_MAX_ASM("[3,2,1,0]", "", "");
   }
   return r;
-#else
-  const float p = dpp_quad<PERM>(a);
-  return vmax(NEG_A ? -p : p, NEG_B ? -b : b);
-#endif
 }
 #undef PR_DPP_MAX_ASM
 
@@ -1265,55 +1049,6 @@ __device__ __forceinline__ void bitonic_merge_vpad(float (&z)[N]) {
   }
 }
 
-__device__ __forceinline__ uint4 ld_raw_u4(const PR_GLOBAL uint4* p) {
-#if PR_CM_RAW_NT
-  return ld_nt_u4(p);
-#else
-  const u32x4_t v = *(const PR_GLOBAL u32x4_t*)p;
-  return make_uint4(v.x, v.y, v.z, v.w);
-#endif
-}
-
-// PR_CM_MEMPROBE (diagnostic, WRONG results; flags-0 timing of the memory phases): bit 1 = no pedestal
-// loads in phase 1, 2 = no gain-factor loads in phase 3, 4 = no raw loads, 8 = no flush stores,
-// 16 = no eligibility-plane loads.  A removed load is replaced by an opaque per-lane value (base
-// gain, every pixel eligible), so the rest of the kernel runs the same instruction stream.
-#ifndef PR_CM_MEMPROBE
-#define PR_CM_MEMPROBE 0
-#endif
-#if PR_CM_MEMPROBE
-template <int NT, bool RAW_IN>
-__device__ __forceinline__ void cm_probe_loads(const PR_GLOBAL uint16_t* raw_t, const PR_GLOBAL uint8_t* pl_t,
-                                               const PR_GLOBAL float* const (&ped_t)[NT], uint32_t o, int tid,
-                                               uint4& rw, uint32_t& ep, float (&pa0)[1][8]) {
-  if constexpr (!RAW_IN) {
-    if constexpr (PR_CM_MEMPROBE & 4) {
-      uint32_t z = 0x01000100u + ((uint32_t)tid & 0xffu) * 0x00010001u;
-      asm volatile("" : "+v"(z));
-      rw = make_uint4(z, z ^ 0x00010001u, z ^ 0x00020002u, z ^ 0x00030003u);
-    } else {
-      rw = ld_raw_u4((const PR_GLOBAL uint4*)(raw_t + o));
-    }
-  }
-  if constexpr (PR_CM_MEMPROBE & 16) {
-    uint32_t z = 0xFFFFFFFFu;
-    asm volatile("" : "+v"(z));
-    ep = z;
-  } else {
-    ep = load_planes_o<NT>(pl_t, o);
-  }
-  if constexpr (PR_CM_MEMPROBE & 1) {
-    for (int j = 0; j < 8; ++j) {
-      uint32_t z = 0x42c80000u + (uint32_t)j;   // ~100.0
-      asm volatile("" : "+v"(z));
-      pa0[0][j] = __uint_as_float(z);
-    }
-  } else {
-    load8o<1>(reinterpret_cast<const PR_GLOBAL float* const(&)[1]>(ped_t), o, 1u, pa0);
-  }
-}
-#endif
-
 // TR / TC: the tile rows / columns as compile-time constants for the production shapes (0 = from
 // TileGeom): every LDS address in the unrolled loops is then a base VGPR + immediate offset.
 // Phase 1, compile-time tile shape: decode + pedestal of the tile into LDS by BLOCK threads
@@ -1334,35 +1069,23 @@ __device__ __forceinline__ void cm_load_net(float* tile, SideCtx& sc, const int 
   constexpr int C8 = TC / 8;
   uint32_t ep[NI];
   float pa0[NI][1][8];
-#if PR_CM_OFF32
   // uniform (SGPR) bases at the tile origin; per item one 32-bit offset
   const PR_GLOBAL uint16_t* raw_t = raw + base;
   const PR_GLOBAL uint8_t* pl_t = (const PR_GLOBAL uint8_t*)planes + CmLayout<NT>::kPlaneBytes * (base >> 3);
   const PR_GLOBAL float* ped_t[NT];
 #pragma unroll
   for (int k = 0; k < NT; ++k) ped_t[k] = (const PR_GLOBAL float*)ped + k * tg.npix + base;
-#endif
 #pragma unroll
   for (int u = 0; u < NI; ++u) {
     const int i = tid + u * BLOCK;
     if ((u + 1) * BLOCK <= NITEMS || i < NITEMS) {
       const int r = i / C8, c = (i % C8) * 8;
-#if PR_CM_OFF32
       const uint32_t o = (uint32_t)(r * tg.panel_cols + c);
-#if PR_CM_MEMPROBE
-      cm_probe_loads<NT, RAW_IN>(raw_t, pl_t, ped_t, o, tid, rw[u], ep[u], pa0[u]);
-#else
-      if constexpr (!RAW_IN) rw[u] = ld_raw_u4((const PR_GLOBAL uint4*)(raw_t + o));
+      // (raw words streamed: non-temporal loads, profiles/r2/pf/read_ceiling.md)
+      if constexpr (!RAW_IN) rw[u] = ld_nt_u4((const PR_GLOBAL uint4*)(raw_t + o));
       if constexpr (SG) ep[u] = 0u;   // eligibility rides in the pedestals' sign bits
       else ep[u] = load_planes_o<NT>(pl_t, o);
       load8o<1>(reinterpret_cast<const PR_GLOBAL float* const(&)[1]>(ped_t), o, 1u, pa0[u]);
-#endif
-#else
-      const int64_t pix = base + (int64_t)r * tg.panel_cols + c;
-      if constexpr (!RAW_IN) rw[u] = ld_raw_u4((const PR_GLOBAL uint4*)(raw + pix));
-      ep[u] = load_planes<NT>(planes, pix);
-      load8<1>(ped, tg.npix, pix, 1u, pa0[u]);
-#endif
     }
   }
 #pragma unroll
@@ -1374,7 +1097,7 @@ __device__ __forceinline__ void cm_load_net(float* tile, SideCtx& sc, const int 
     float x[8];
     uint32_t el = 0xFFu, cb = 0;
     if (act) {
-      if (PR_CM_BASE_FAST && NT > 1 && __builtin_amdgcn_ballot_w64(!cm_base_only<KIND>(rw[u])) == 0) {
+      if (NT > 1 && __builtin_amdgcn_ballot_w64(!cm_base_only<KIND>(rw[u])) == 0) {
         // wave-uniform: no switched pixel
         if constexpr (SG) {
           el = cm_decode8_base_sg<KIND>(rw[u], pa0[u][0], v, x) ? 0u : 0xFFu;   // only el != 0xFF is read
@@ -1387,11 +1110,7 @@ __device__ __forceinline__ void cm_load_net(float* tile, SideCtx& sc, const int 
 #pragma unroll
         for (int j = 0; j < 8; ++j) pa[0][j] = pa0[u][0][j];
         if constexpr (NT > 1) {
-#if PR_CM_OFF32
           load8o<NT>(ped_t, (uint32_t)(r * tg.panel_cols + c), need_from_raw<NT>(rw[u]), pa, 1);
-#else
-          load8<NT>(ped, tg.npix, base + (int64_t)r * tg.panel_cols + c, need_from_raw<NT>(rw[u]), pa, 1);
-#endif
         }
         cm_decode8<KIND, NT, SG>(rw[u], ep[u], pa, v, el, cb);
         cm_tile_values(v, el, x);
@@ -1411,7 +1130,7 @@ __device__ __forceinline__ void cm_load_net(float* tile, SideCtx& sc, const int 
       const int i = tid + u * BLOCK;
       if ((u + 1) * BLOCK <= NITEMS || i < NITEMS) {
         const int r = i / C8, c = (i % C8) * 8;
-        rw[u] = ld_raw_u4((const PR_GLOBAL uint4*)(raw_next + base + (int64_t)r * tg.panel_cols + c));
+        rw[u] = ld_nt_u4((const PR_GLOBAL uint4*)(raw_next + base + (int64_t)r * tg.panel_cols + c));
       }
     }
   }
@@ -1479,20 +1198,13 @@ __device__ __forceinline__ void cm_rows(float* tile, const int P, const int R, c
   }
 }
 
-// PR_CM_COL_ONELOAD = 1: the column phase reads its values from LDS once (pass 2 from registers)
-#ifndef PR_CM_COL_ONELOAD
-#define PR_CM_COL_ONELOAD 1
-#endif
-// PR_CM_PK_COLSUB = 0: the column correction one v_sub_f32 per row (A/B of the packed form)
-#ifndef PR_CM_PK_COLSUB
-#define PR_CM_PK_COLSUB 1
-#endif
 // Column medians, FOUR lanes (a quad) per column, M rows each (t0 a multiple of 4).
 //  Sign domain: the odd lane of each pair (q = 1, 3) holds its values NEGATED, so both lanes of a
 //  pair run identical instructions where the classic merge-split needs lane-dependent min / max:
-//   1. pass 1 counts the participants (|v| < thr); the quad's totals fix how many non-participants
-//      become -inf (the rest +inf: balanced padding puts the median at fixed ranks 2M-1, 2M);
-//      pass 2 reloads the column and writes sign-domain values and pads (no NaN survives);
+//   1. pass 1 reads the column from LDS into registers (once: profiles/r5/README.md) and counts the
+//      participants (|v| < thr); the quad's totals fix how many non-participants become -inf (the
+//      rest +inf: balanced padding puts the median at fixed ranks 2M-1, 2M); pass 2 turns the
+//      registers into sign-domain values and pads (no NaN survives);
 //   2. every lane sorts its M values ascending (sort_regs<M>);
 //   3. level 1, lanes (q, q^1): z[i] = max(partner[i], -x[i]) is the V-shaped merge-split half for
 //      BOTH lanes (even lane: -min(l[i], u[M-1-i]); odd lane: max(l[i], u[M-1-i])), one DPP fetch
@@ -1520,9 +1232,7 @@ __device__ __forceinline__ void cm_cols(float* tile, const int P, const int R, c
     float* colp = tile + 2 * q * P + c;
     auto row_of = [&](int i) { return 8 * (i >> 1) + 2 * q + (i & 1); };
     auto off_of = [&](int i) { return (8 * (i >> 1) + (i & 1)) * P; };
-    auto load = [&](int i) { return (act && row_of(i) < R) ? colp[off_of(i)] : QNAN; };
     float x[M];
-#if PR_CM_COL_ONELOAD
     // ONE pass over LDS: the column into registers, participants counted on the way (inactive lanes
     // -- whole quads past the tile's columns -- read column 0 and never write: no per-element select)
     int my_cnt = 0;
@@ -1532,15 +1242,6 @@ __device__ __forceinline__ void cm_cols(float* tile, const int P, const int R, c
       my_cnt += fabsf(x[i]) < cp.thr ? 1 : 0;
       if ((i & 15) == 15) asm volatile("" ::: "memory");
     }
-#else
-    // pass 1: participants of this lane
-    int my_cnt = 0;
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      my_cnt += fabsf(load(i)) < cp.thr ? 1 : 0;
-      if ((i & 15) == 15) asm volatile("" ::: "memory");
-    }
-#endif
     // quad totals + exclusive prefix of the non-participants: balanced +-inf padding
     const int my_inv = M - my_cnt;
     const int i0 = dpp_quad_i<0x00>(my_inv), i1 = dpp_quad_i<0x55>(my_inv);
@@ -1556,7 +1257,7 @@ __device__ __forceinline__ void cm_cols(float* tile, const int P, const int R, c
     asm volatile("" : "+v"(pad_base));   // one v_bitop3 per pad below, not bitop3 + xor
 #pragma unroll
     for (int i = 0; i < M; ++i) {
-      const float v = PR_CM_COL_ONELOAD ? x[i] : load(i);
+      const float v = x[i];
       const bool pt = fabsf(v) < cp.thr;
       const uint32_t padb = ((uint32_t)s & 0x80000000u) ^ pad_base;
       x[i] = __uint_as_float(pt ? (__float_as_uint(v) ^ flip) : padb);
@@ -1592,14 +1293,13 @@ __device__ __forceinline__ void cm_cols(float* tile, const int P, const int R, c
       const f32x2_t m2 = {med, med};
 #pragma unroll
       for (int i = 0; i < M; i += 2) {
-        if (PR_CM_PK_COLSUB && row_of(i + 1) < R) {
+        if (row_of(i + 1) < R) {
           f32x2_t v = {colp[off_of(i)], colp[off_of(i + 1)]};
           v -= m2;
           colp[off_of(i)] = v.x;
           colp[off_of(i + 1)] = v.y;
         } else {
           if (row_of(i) < R) colp[off_of(i)] -= med;
-          if (!PR_CM_PK_COLSUB && row_of(i + 1) < R) colp[off_of(i + 1)] -= med;
         }
         if ((i & 14) == 14) asm volatile("" ::: "memory");
       }
@@ -1607,30 +1307,13 @@ __device__ __forceinline__ void cm_cols(float* tile, const int P, const int R, c
   }
 }
 
-// PR_CM_MAX_VGPR > 0: cap the net kernel's VGPRs (diagnostic builds: leave room on each SIMD for
-// a co-resident consumer kernel's wave)
-#ifndef PR_CM_MAX_VGPR
-#define PR_CM_MAX_VGPR 0
-#endif
-#if PR_CM_MAX_VGPR > 0
-#define PR_CM_VGPR_ATTR __attribute__((amdgpu_num_vgpr(PR_CM_MAX_VGPR / 2)))   // gfx950: the request counts twice (VGPR + AGPR file)
-#else
-#define PR_CM_VGPR_ATTR
-#endif
-#ifndef PR_CM_NET_MAXNI
-#define PR_CM_NET_MAXNI 8
-#endif
-// signed pedestal tables for the production shapes (0: always the bit-planes, the A/B build)
-#ifndef PR_CM_SG
-#define PR_CM_SG 1
-#endif
-// Jungfrau stripe width: 128 (one 256x128 tile per CU, 512 threads) or 64 (two 256x64 tiles per CU,
-// 256 threads each -- one workgroup's median phases overlap the other's memory phases)
-#ifndef PR_CM_JF_W
-#define PR_CM_JF_W 64
-#endif
+// Compile-time phase-1 / store form: at most this many 8-pixel items per lane (the Jungfrau stripes)
+constexpr int kNetMaxItems = 8;
+// Jungfrau stripe width: two 256x64 tiles per CU, 256 threads each -- one workgroup's median phases
+// overlap the other's memory phases (one 256x128 tile on 512 threads: profiles/r5/README.md)
+constexpr int kJfStripeCols = 64;
 template <int KIND, int L, int M, int BLOCK, int TR = 0, int TC = 0, bool SG = false>
-__global__ __launch_bounds__(BLOCK, M <= 48 ? (BLOCK / 64) * PR_CM_EPIX_WG_PER_CU / 4 : 2) PR_CM_VGPR_ATTR void calib_cm_net_kernel(
+__global__ __launch_bounds__(BLOCK, M <= 48 ? (BLOCK / 64) * kEpixWgPerCu / 4 : 2) void calib_cm_net_kernel(
     const FramePtrs fp, const float* __restrict__ ped, const float* __restrict__ gf,
     const uint8_t* __restrict__ planes, const TileGeom tg, const CmParams cp, const ImgOut io) {
   constexpr int NT = KIND == kEpix10ka ? 2 : (KIND == kJungfrau ? 3 : 1);
@@ -1641,14 +1324,14 @@ __global__ __launch_bounds__(BLOCK, M <= 48 ? (BLOCK / 64) * PR_CM_EPIX_WG_PER_C
   float* tile = reinterpret_cast<float*>(smem);
   float* side = tile + R * P;
   SideCtx sc = side_ctx(side, tg.side_slots);
-  const TileCoord t = cm_coords(tg, R, C, (int)blockIdx.x, io.desc);
+  const TileCoord t = cm_coords(tg, R, C);
   const int tid = threadIdx.x;
   constexpr int NITEMS = (TR > 0 && TC > 0) ? TR * (TC / 8) : 0;
   constexpr int NI = NITEMS > 0 ? (NITEMS + BLOCK - 1) / BLOCK : 0;
   // compile-time phase-1 / store form when every lane's items fit in registers: up to 6 items at the
-  // epix10k2M kernel's 128-VGPR budget (four workgroups per CU), up to PR_CM_NET_MAXNI (8) for the
-  // Jungfrau 256x128 stripe, whose 135-KB tile allows one workgroup per CU (256 VGPRs)
-  constexpr bool kNet = NI > 0 && NI <= (M <= 48 ? 6 : PR_CM_NET_MAXNI);
+  // epix10k2M kernel's 128-VGPR budget (four workgroups per CU), up to kNetMaxItems for the
+  // Jungfrau stripes (two workgroups per CU, 256 VGPRs)
+  constexpr bool kNet = NI > 0 && NI <= (M <= 48 ? 6 : kNetMaxItems);
   // signed pedestals (no bit-planes, `planes` may be null) only in the compile-time phase-1 / store form
   static_assert(!SG || kNet, "calib_cm_net_kernel: signed pedestal tables need the compile-time tile form");
   // frames of this workgroup (tg.fpw consecutive frames of one tile; the compile-time production
@@ -1691,18 +1374,9 @@ __global__ __launch_bounds__(BLOCK, M <= 48 ? (BLOCK / 64) * PR_CM_EPIX_WG_PER_C
       cm_phase1<KIND, NT>(tile, sc, P, R, C, tg, raw, pedp, plp, tb);
     }
     PR_STAMP(1);
-    // PR_CM_GPRE: the first gain table of every item is loaded now and arrives during the medians,
-    // so the store phase has no memory round trip before its first output (+40 VGPRs)
+    // (loading the first gain table here, to arrive during the medians, costs 40 VGPRs and a
+    // workgroup per CU: profiles/r5/README.md section 4)
     float g0[kNet ? NI : 1][1][8];
-    if constexpr (kNet && PR_CM_GPRE) {
-      constexpr int C8 = TC / 8;
-#pragma unroll
-      for (int u = 0; u < NI; ++u) {
-        const int i = tid + u * BLOCK;
-        if ((u + 1) * BLOCK <= NITEMS || i < NITEMS)
-          load8<1>(gfp, tg.npix, tb + (int64_t)(i / C8) * tg.panel_cols + (i % C8) * 8, 1u, g0[u]);
-      }
-    }
     __syncthreads();
     PR_STAMP(2);
 
@@ -1729,32 +1403,17 @@ __global__ __launch_bounds__(BLOCK, M <= 48 ? (BLOCK / 64) * PR_CM_EPIX_WG_PER_C
       // (the first gain table of every item up front; the switched-gain tables are rare and are
       // loaded per item, which keeps the production kernel within 128 VGPRs)
       uint32_t cbs[NI], slots[NI];
-#if PR_CM_OFF32
       const PR_GLOBAL float* gf_t[NT];
 #pragma unroll
       for (int k = 0; k < NT; ++k) gf_t[k] = (const PR_GLOBAL float*)gfp + k * tg.npix + tb;
-#endif
 #pragma unroll
       for (int u = 0; u < NI; ++u) {
         const int i = tid + u * BLOCK;
         if ((u + 1) * BLOCK <= NITEMS || i < NITEMS) {
           const int r = i / C8, k = i % C8, c = k * 8;
           cm_get_meta<NT>(reinterpret_cast<const uint8_t*>(tile + r * P + C), C, k, cbs[u], slots[u]);
-#if PR_CM_OFF32
-#if PR_CM_MEMPROBE & 2
-          for (int j = 0; j < 8; ++j) {
-            uint32_t z = 0x3f800000u + (uint32_t)j;
-            asm volatile("" : "+v"(z));
-            g0[u][0][j] = __uint_as_float(z);
-          }
-#else
-          if constexpr (!PR_CM_GPRE)
-            load8o<1>(reinterpret_cast<const PR_GLOBAL float* const(&)[1]>(gf_t), (uint32_t)(r * tg.panel_cols + c), 1u,
-                      g0[u]);
-#endif
-#else
-          if constexpr (!PR_CM_GPRE) load8<1>(gfp, tg.npix, tb + (int64_t)r * tg.panel_cols + c, 1u, g0[u]);
-#endif
+          load8o<1>(reinterpret_cast<const PR_GLOBAL float* const(&)[1]>(gf_t), (uint32_t)(r * tg.panel_cols + c), 1u,
+                    g0[u]);
         }
       }
 #pragma unroll
@@ -1767,15 +1426,11 @@ __global__ __launch_bounds__(BLOCK, M <= 48 ? (BLOCK / 64) * PR_CM_EPIX_WG_PER_C
 #pragma unroll
           for (int j = 0; j < 8; ++j) ga[0][j] = g0[u][0][j];
           float o[8];
-          if (PR_CM_BASE_FAST && NT > 1 && __builtin_amdgcn_ballot_w64(cbs[u] != 0u) == 0) {
+          if (NT > 1 && __builtin_amdgcn_ballot_w64(cbs[u] != 0u) == 0) {
             // wave-uniform: every pixel of the item takes the table-0 gain factor
             cm_out8<KIND, NT, true, SG>(tile + r * P + c, side, cbs[u], slots[u], ga, raw, pedp, tg.npix, pix, o);
           } else {
-#if PR_CM_OFF32
             if constexpr (NT > 1) load8o<NT>(gf_t, (uint32_t)(r * tg.panel_cols + c), cm_need<NT>(cbs[u]), ga, 1);
-#else
-            if constexpr (NT > 1) load8<NT>(gfp, tg.npix, pix, cm_need<NT>(cbs[u]), ga, 1);
-#endif
             cm_out8<KIND, NT, false, SG>(tile + r * P + c, side, cbs[u], slots[u], ga, raw, pedp, tg.npix, pix, o);
           }
           cm_put8(tile + r * P + c, o);
@@ -1796,7 +1451,7 @@ __global__ __launch_bounds__(BLOCK, M <= 48 ? (BLOCK / 64) * PR_CM_EPIX_WG_PER_C
   };
   if constexpr (kNet) {
 #pragma unroll
-    for (int fi = 0; fi < PR_CM_FPW; ++fi)   // straight-line frames (a loop hoists every address)
+    for (int fi = 0; fi < 1; ++fi)   // straight-line frames (a loop hoists every address)
       if (fi < nf) frame(fi);
   } else {
     for (int fi = 0; fi < nf; ++fi) frame(fi);
@@ -1819,9 +1474,8 @@ __global__ __launch_bounds__(BLOCK, M <= 48 ? (BLOCK / 64) * PR_CM_EPIX_WG_PER_C
 // The production shapes whose compile-time kernels read the signed pedestal tables (launch_calib_cm
 // picks them with the same predicate); Calibrator builds the tables only for these.
 bool cm_signed_shape(int kind, int asic_rows, int asic_cols, int bank_cols) {
-  if (!PR_CM_SG) return false;
   if (kind == kEpix10ka) return bank_cols == 48 && asic_rows == 176 && asic_cols % 48 == 0;
-  if (kind == kJungfrau) return PR_CM_NET_MAXNI >= 8 && bank_cols == 64 && asic_rows == 256 && asic_cols % 128 == 0;
+  if (kind == kJungfrau) return bank_cols == 64 && asic_rows == 256 && asic_cols % 128 == 0;
   return false;
 }
 
@@ -1868,7 +1522,7 @@ void launch_calib_cm(const FramePtrs& fp, int nframes, uint64_t ped, uint64_t gf
   //  * epix10k2M (176-row ASICs, 48-column banks): one-bank 176x48 stripes on 256-thread blocks,
   //    four workgroups per CU (round 1: 8.8 us/frame vs 9.2 for 176x96, 15.8 full width);
   //  * Jungfrau (256x256 ASICs, 64-column banks): 256x64 stripes (one bank), 256-thread blocks, two
-  //    workgroups per CU (PR_CM_JF_W; 256x128 on 512 threads, one per CU: 52.8 vs 37.3 us/frame);
+  //    workgroups per CU (kJfStripeCols; 256x128 on 512 threads, one per CU: 52.8 vs 37.3 us/frame);
   //  * otherwise: the widest stripe <= 128 columns whose tile fits half the LDS (two blocks per CU)
   //    when a compile-time network exists for the shape, else the widest that fits at all.
   const int M4 = (asic_rows + 3) / 4;
@@ -1880,7 +1534,7 @@ void launch_calib_cm(const FramePtrs& fp, int nframes, uint64_t ped, uint64_t gf
   if (epix_prod) {
     max_w = 48;
   } else if (jf_prod) {
-    max_w = PR_CM_JF_W;
+    max_w = kJfStripeCols;
   } else if (net) {
     for (int w = std::min(asic_cols, 128); w >= bank_cols; --w)
       if (asic_cols % w == 0 && w % bank_cols == 0 && w % 8 == 0 && cm_lds_bytes(asic_rows, w, kind) <= 80 * 1024) {
@@ -1903,17 +1557,15 @@ void launch_calib_cm(const FramePtrs& fp, int nframes, uint64_t ped, uint64_t gf
   // signed pedestal tables (eligibility in the sign bits, no bit-plane loads): the production kernels,
   // whose phase 1 is the compile-time form (cm_load_net); the loop form (cm_phase1 / cm_store) of the
   // other shapes reads the bit-planes
-  // (-DPR_CM_SG=0: always the bit-planes, the A/B build)
-  if (!PR_CM_SG) ped_sg = 0;
   const float* PS = reinterpret_cast<const float*>(ped_sg);
   const bool sg_kernel = ((epix_prod && asic_cols == 48) ||
-                          (jf_prod && asic_cols == PR_CM_JF_W && PR_CM_NET_MAXNI >= 8)) && ped_sg != 0;
+                          (jf_prod && asic_cols == kJfStripeCols)) && ped_sg != 0;
   check(sg_kernel || planes != 0, "calib_cm: this shape needs the eligibility bit-planes");
-  // LDS budget of one workgroup: the epix10k2M 176x48 stripe runs PR_CM_EPIX_WG_PER_CU workgroups
+  // LDS budget of one workgroup: the epix10k2M 176x48 stripe runs kEpixWgPerCu workgroups
   // per CU, the two 256x64 Jungfrau stripes two, the narrow compile-time kernels two,
   // everything else one; what the tiles leave is side slots
   const size_t lds_tiles = lds;
-  const size_t budget = (epix_prod && asic_cols == 48) ? (160 * 1024) / PR_CM_EPIX_WG_PER_CU
+  const size_t budget = (epix_prod && asic_cols == 48) ? (160 * 1024) / kEpixWgPerCu
                         : (jf_prod && asic_cols == 64) ? 80 * 1024     // two 256x64 Jungfrau stripes per CU
                         : (net && !jf_prod && asic_cols <= 128) ? 80 * 1024
                                                                 : 160 * 1024;
@@ -1928,12 +1580,12 @@ void launch_calib_cm(const FramePtrs& fp, int nframes, uint64_t ped, uint64_t gf
   tg.plain_mask = plain_mask;
   tg.npix = (int64_t)n_panels * panel_rows * panel_cols;
   tg.nframes = nframes;
-  // frames per workgroup: the epix10k2M production kernel takes PR_CM_FPW consecutive frames of
-  // its tile (next frame's raw words prefetched during the medians); everything else one
-  tg.fpw = (epix_prod && asic_cols == 48) ? PR_CM_FPW : 1;
+  // frames per workgroup: one (two, with the next frame's raw words prefetched during the medians,
+  // measured equal or slower: profiles/r3/cm/cm_kernel_r3.md, profiles/r5/README.md section 4)
+  tg.fpw = 1;
   tg.side_slots = side_slots;
   tg.pitch = cm_pitch(asic_cols, kind == kJungfrau ? 2 : 1);
-  tg.xcd_map = (nframes <= PR_CM_XCD_MAX_FRAMES &&
+  tg.xcd_map = (nframes <= kXcdMaxFrames &&
                 ((int64_t)n_panels * tg.asics_per_col * tg.asics_per_row) % 8 == 0) ? 1 : 0;
   const CmParams cp{thr, maxcorr, npix_min, flags, bank_cols};
   const dim3 grid((unsigned)(n_panels * tg.asics_per_col * tg.asics_per_row * ((nframes + tg.fpw - 1) / tg.fpw)));
@@ -1944,19 +1596,17 @@ void launch_calib_cm(const FramePtrs& fp, int nframes, uint64_t ped, uint64_t gf
   const bool narrow = asic_cols <= 128;
   const size_t lds_all = lds_tiles + 32 * (size_t)side_slots;
   if (sg_kernel && epix_prod) {
-    cm_launch(calib_cm_net_kernel<kEpix10ka, 48, 44, PR_CM_EPIX_BLOCK, 176, 48, true>, grid, PR_CM_EPIX_BLOCK, lds_all, s,
-              fp, PS, G, nullptr, tg, cp, io);
+    cm_launch(calib_cm_net_kernel<kEpix10ka, 48, 44, kEpixBlock, 176, 48, true>, grid, kEpixBlock, lds_all, s, fp, PS,
+              G, nullptr, tg, cp, io);
   } else if (sg_kernel) {
-#if PR_CM_NET_MAXNI >= 8
-    cm_launch(calib_cm_net_kernel<kJungfrau, 64, 64, 4 * PR_CM_JF_W, 256, PR_CM_JF_W, true>, grid, 4 * PR_CM_JF_W,
-              lds_all, s, fp, PS, G, nullptr, tg, cp, io);
-#endif
+    cm_launch(calib_cm_net_kernel<kJungfrau, 64, 64, 4 * kJfStripeCols, 256, kJfStripeCols, true>, grid,
+              4 * kJfStripeCols, lds_all, s, fp, PS, G, nullptr, tg, cp, io);
   } else if (epix_prod && asic_cols == 48) {
-    cm_launch(calib_cm_net_kernel<kEpix10ka, 48, 44, PR_CM_EPIX_BLOCK, 176, 48>, grid, PR_CM_EPIX_BLOCK, lds_all, s, fp, P,
-              G, F, tg, cp, io);
-  } else if (jf_prod && asic_cols == PR_CM_JF_W) {
-    cm_launch(calib_cm_net_kernel<kJungfrau, 64, 64, 4 * PR_CM_JF_W, 256, PR_CM_JF_W>, grid, 4 * PR_CM_JF_W, lds_all, s,
-              fp, P, G, F, tg, cp, io);
+    cm_launch(calib_cm_net_kernel<kEpix10ka, 48, 44, kEpixBlock, 176, 48>, grid, kEpixBlock, lds_all, s, fp, P, G, F,
+              tg, cp, io);
+  } else if (jf_prod && asic_cols == kJfStripeCols) {
+    cm_launch(calib_cm_net_kernel<kJungfrau, 64, 64, 4 * kJfStripeCols, 256, kJfStripeCols>, grid, 4 * kJfStripeCols,
+              lds_all, s, fp, P, G, F, tg, cp, io);
   } else if (kind == kEpix10ka && bank_cols == 48 && M4 == 44 && narrow) {
     cm_launch(calib_cm_net_kernel<kEpix10ka, 48, 44, 512>, grid, 512, lds_all, s, fp, P, G, F, tg, cp, io);
   } else if (kind == kEpix10ka && bank_cols == 8 && M4 == 4 && narrow) {

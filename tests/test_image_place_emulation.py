@@ -1,6 +1,6 @@
 """CPU emulation of the fused CM -> image write-out's index math (csrc/common_mode.hip, cm_place):
 every thread of a 256-thread workgroup walks its (run, full chunk) items incrementally (row-run
-panels; column-run panels: the line-aligned walk, PR_CM_PLACE_LA, or the round-5 4-chunk walk), then
+panels; column-run panels: the line-aligned walk), then
 the ragged run ends; the emulation applies the same arithmetic to every tile of the production
 epix10k2M geometry (and the small test detectors) and checks that each panel pixel is written
 exactly once, at the image element the geometry assigns it, that full chunks are 16-B aligned, and
@@ -15,7 +15,7 @@ from psana_ray_amd.models import get_detector, list_detectors
 from psana_ray_amd.models.geometry import make_geometry
 
 
-def _place_tile(writes, P, R, C, desc, y0, x0, nb=256, la=True):
+def _place_tile(writes, P, R, C, desc, y0, x0, nb=256):
     """Transcription of cm_place: (image element, tile row, tile col, full chunk, instruction id)
     per element written; the instruction id is (wave, iteration) of the line-aligned walk."""
     b, sy, sx = (int(v) for v in desc)
@@ -43,7 +43,7 @@ def _place_tile(writes, P, R, C, desc, y0, x0, nb=256, la=True):
         i = t if step > 0 else ln - 1 - t
         return (run, i) if rows else (i, run)
 
-    if nfull > 0 and not rows and la:
+    if nfull > 0 and not rows:
         ob = (lo & ~3) + 4 * ch_lo
         nrg, ng, nw = (nruns + 7) >> 3, (nfull + 14) >> 3, nb // 64
         for wave in range(nw):
@@ -60,20 +60,17 @@ def _place_tile(writes, P, R, C, desc, y0, x0, nb=256, la=True):
                         for q in range(4):
                             r, c = tile_rc(run, t_lo + 4 * k + q)
                             out.append((base + q, r, c, True, (wave, u)))
-    elif nfull > 0:
-        span = nfull if rows else ((nfull + 3) >> 2) * 4
-        per = nfull if rows else 4 * nruns
+    elif nfull > 0:   # row-run panels: (run, chunk) run-major, consecutive lanes consecutive chunks
+        per = nfull
         da, dw = nb // per, nb - (nb // per) * per
-        outer_n = nruns if rows else (span >> 2)
         for tid in range(nb):
             a, w = divmod(tid, per)
-            while a < outer_n:
-                run = a if rows else (w >> 2)
-                k = w if rows else 4 * a + (w & 3)
+            while a < nruns:
+                run, k = a, w
                 if k < nfull:
                     base = (lo & ~3) + run * outer + 4 * (ch_lo + k)
                     assert base % 4 == 0
-                    # the lean form (PR_CM_PLACE2): linear in (run, chunk), signed tile stride
+                    # the kernel's form: linear in (run, chunk), signed tile stride
                     ob = (lo & ~3) + 4 * ch_lo
                     assert ob + run * outer + 4 * k == base
                     t0 = t_lo + 4 * k
@@ -96,9 +93,8 @@ def _place_tile(writes, P, R, C, desc, y0, x0, nb=256, la=True):
     return out
 
 
-@pytest.mark.parametrize("la", [True, False])
 @pytest.mark.parametrize("det", ["epix10k2M"] + [d for d in list_detectors() if d.startswith("tiny")])
-def test_cm_place_index_math(det, la):
+def test_cm_place_index_math(det):
     spec = get_detector(det)
     geo = make_geometry(spec)
     place = geo.panel_placement()
@@ -113,7 +109,7 @@ def test_cm_place_index_math(det, la):
     for p in range(Pn):
         for ar in range(H // R):
             for ac in range(W // C):
-                writes = _place_tile(hits, 0, R, C, place[p], ar * R, ac * C, la=la)
+                writes = _place_tile(hits, 0, R, C, place[p], ar * R, ac * C)
                 for addr, r, c, _full, _ins in writes:
                     hits[addr] += 1
                     assert imap[addr] == p * H * W + (ar * R + r) * W + (ac * C + c)

@@ -77,7 +77,7 @@ def test_common_mode_bitwise(cuda_device, det, flags):
 @pytest.mark.parametrize("det", ["epix10k2M", "jungfrau4M", "tiny_epix"])
 def test_common_mode_switched_and_unswitched_waves_bitwise(cuda_device, det):
     """The decode / store phases take a wave-uniform fast path for items with no gain-switched pixel
-    (PR_CM_BASE_FAST) and the general path otherwise: frames whose left half has a gain-switch bit on
+    (the base-table fast path) and the general path otherwise: frames whose left half has a gain-switch bit on
     ~7 % of the pixels (every wave there takes the general path) and whose right half has none (every
     wave takes the fast path), Jungfrau also with its invalid gain code, bitwise against the golden."""
     spec = get_detector(det)

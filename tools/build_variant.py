@@ -3,7 +3,7 @@
 scheduler strategy or a -D constant), linked with the shipped objects into variants/_C_<name>.so.
 
     python tools/build_variant.py maxilp common_mode.hip -mllvm -amdgpu-sched-strategy=max-ilp
-    VARIANTS="maxilp" PROBE=tools/cm_probe.py gpurun -- bash tools/gpu_variants.sh
+    VARIANTS="maxilp" PROBE=tools/cm_probe.py bash tools/gpu_ab.sh     (on the GPU box)
 """
 import subprocess
 import sys
