@@ -287,6 +287,65 @@ def main(argv=None):
                     "pack_us_per_frame": round(t_pack[0] * 1e6 / FR, 3), "pack_share": round(t_pack[0] / ms[0], 3),
                     "rounds_us_per_frame": us(t_sp[k]), "vs_read_floor": round(ms[0] / mr[0], 3),
                     "vs_radial": round(ms[0] / mrad[0], 3)}, frames=FR)
+    if want("powder"):
+        # K-11 powder statistics: 64 SEPARATELY allocated calib frames (ring slots are not contiguous),
+        # and the read floor on the SAME frames in the same process -- alternating rounds, the median
+        # round of each.  Three cases: one class; two classes with 1 frame in 16 a hit; two classes
+        # with every frame a hit (class 0 untouched).  Bytes: 4 B per pixel and frame plus one
+        # read-modify-write of the accumulator words of every class with a frame in the batch (28 B
+        # per pixel and class, each way): 1.22x the floor's bytes with one class touched, 1.44x with two.
+        from psana_ray_amd.ops.reference import (POWDER_FRAC_BITS, POWDER_QMAX_NONE, POWDER_THR_ABOVE, POWDER_VMAX,
+                                                 POWDER_VMIN)
+
+        FR, rounds = 64, 5
+        C = _ext.load()
+        praw = [pool[i % pool.shape[0]].to(dev).clone() for i in range(FR)]
+        pfl = [torch.empty(spec.frame_shape, dtype=torch.float32, device=dev) for _ in range(FR)]
+        cal.run(praw, pfl)
+        torch.cuda.synchronize()
+        pflat = [t.reshape(-1) for t in pfl]
+        fp64 = [int(t.data_ptr()) for t in pfl]
+        sums = torch.zeros(FR, dtype=torch.float32, device=dev)
+
+        def acc_set(nc):
+            return (torch.zeros(nc, dtype=torch.int64, device=dev), torch.zeros((nc, npix), dtype=torch.int32, device=dev),
+                    torch.zeros((nc, npix), dtype=torch.int64, device=dev),
+                    torch.zeros((nc, npix), dtype=torch.int64, device=dev),
+                    torch.full((nc, npix), POWDER_QMAX_NONE, dtype=torch.int32, device=dev),
+                    torch.zeros((nc, npix), dtype=torch.int32, device=dev))
+
+        def reset(acc):   # every timed window starts a run (it stays far below max_frames)
+            for t, v in zip(acc, (0, 0, 0, 0, POWDER_QMAX_NONE, 0)):
+                t.fill_(v)
+
+        cases = [("NC=1", None, 1),
+                 ("NC=2, 1 hit in 16", torch.tensor([int(f % 16 == 0) for f in range(FR)], dtype=torch.int32, device=dev), 2),
+                 ("NC=2, all hits", torch.ones(FR, dtype=torch.int32, device=dev), 1)]
+        accs = [acc_set(1 if keys is None else 2) for _, keys, _ in cases]
+
+        def pw(k):
+            keys = cases[k][1]
+            return lambda: kernels.powder_accumulate(pflat, POWDER_VMIN, POWDER_VMAX, POWDER_FRAC_BITS, POWDER_THR_ABOVE,
+                                                     *accs[k], keys=keys, key_min=1)
+
+        t_read, t_pw = [], [[] for _ in cases]
+        for _ in range(rounds):
+            t_read.append(timeit(lambda: C.read_f32(fp64, npix, 16, False, int(sums.data_ptr()), _ext.stream_handle()),
+                                 a.iters))
+            for k in range(len(cases)):
+                reset(accs[k])
+                t_pw[k].append(timeit(pw(k), a.iters))
+        med = lambda ts: sorted(ts)[rounds // 2]   # noqa: E731
+        us = lambda ts: [round(t[0] * 1e6 / FR, 3) for t in ts]   # noqa: E731
+        mr = med(t_read)
+        report("read_f32 reference (K=16)", mr, FR * npix * 4, {"rounds_us_per_frame": us(t_read)}, frames=FR)
+        for k, (name, keys, touched) in enumerate(cases):
+            mp = med(t_pw[k])
+            nbytes = FR * npix * 4 + touched * npix * 56
+            report(f"powder({name})", mp, nbytes,
+                   {"classes_touched": touched, "rounds_us_per_frame": us(t_pw[k]),
+                    "bytes_vs_read_floor": round(nbytes / (FR * npix * 4), 3),
+                    "vs_read_floor": round(mp[0] / mr[0], 3), "TB_per_s": round(nbytes / mp[0] / 1e12, 3)}, frames=FR)
     if want("h2d"):
         C = _ext.load()
         hp = src.pool

@@ -97,7 +97,8 @@ static FramePtrs make_ptrs(const std::vector<uint64_t>& in, const std::vector<ui
   return fp;
 }
 
-// The consumers' ring-slot bindings (peakfind_slots, radial_slots, dark_slots, sparsify_slots): the two
+// The consumers' ring-slot bindings (peakfind_slots, radial_slots, dark_slots, sparsify_slots,
+// powder_slots): the two
 // checks they share, then fn(index of the chunk's first slot, its slot pointers) for every chunk of at
 // most kMaxFrames slots.
 template <class Fn>
@@ -406,6 +407,32 @@ PYBIND11_MODULE(_C, m) {
         py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("n"), py::arg("thr"), py::arg("vmax"),
         py::arg("cap"), py::arg("mask"), py::arg("keys"), py::arg("key_min"), py::arg("nnz"), py::arg("flags"),
         py::arg("offs"), py::arg("pix"), py::arg("val"), py::arg("scratch"), py::arg("scratch_bytes"),
+        py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+
+  m.def("powder",
+        [](const std::vector<uint64_t>& in, int64_t n, float vmin, float vmax, int frac_bits, float thr_above, int nc,
+           uint64_t keys, int key_min, uint64_t nfr, uint64_t cnt, uint64_t sum, uint64_t sq, uint64_t qmax,
+           uint64_t above, uint64_t stream) {
+          pr::launch_powder(make_ptrs(in, in), (int)in.size(), n, vmin, vmax, frac_bits, thr_above, nc, keys, key_min,
+                            nfr, cnt, sum, sq, qmax, above, stream);
+        },
+        py::arg("in_ptrs"), py::arg("n"), py::arg("vmin"), py::arg("vmax"), py::arg("frac_bits"), py::arg("thr_above"),
+        py::arg("nc"), py::arg("keys"), py::arg("key_min"), py::arg("nfr"), py::arg("cnt"), py::arg("sum"),
+        py::arg("sq"), py::arg("qmax"), py::arg("above"), py::arg("stream"),
+        "K-11 powder statistics: adds up to 64 float32 frames into nfr / cnt / sum / sq / qmax / above [NC, n]");
+  // consumer hot path: ring slots -> powder accumulators, one native call
+  m.def("powder_slots",
+        [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int64_t n, float vmin,
+           float vmax, int frac_bits, float thr_above, int nc, uint64_t keys, int key_min, uint64_t nfr, uint64_t cnt,
+           uint64_t sum, uint64_t sq, uint64_t qmax, uint64_t above, uint64_t stream) {
+          for_slot_chunks(pool, slot_bytes, slots, n * 4, "powder_slots", [&](int a, const std::vector<uint64_t>& in) {
+            pr::launch_powder(make_ptrs(in, in), (int)in.size(), n, vmin, vmax, frac_bits, thr_above, nc,
+                              keys != 0 ? keys + (uint64_t)a * 4 : 0, key_min, nfr, cnt, sum, sq, qmax, above, stream);
+          });
+        },
+        py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("n"), py::arg("vmin"), py::arg("vmax"),
+        py::arg("frac_bits"), py::arg("thr_above"), py::arg("nc"), py::arg("keys"), py::arg("key_min"),
+        py::arg("nfr"), py::arg("cnt"), py::arg("sum"), py::arg("sq"), py::arg("qmax"), py::arg("above"),
         py::arg("stream"), py::call_guard<py::gil_scoped_release>());
 
   m.def("copy_h2d_kernel",

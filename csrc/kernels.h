@@ -87,4 +87,13 @@ void launch_sparsify(const FramePtrs& fp, int nframes, int64_t n, float thr, flo
                      uint64_t keys, int key_min, uint64_t nnz, uint64_t flags, uint64_t offs, uint64_t pix,
                      uint64_t val, uint64_t scratch, int64_t scratch_bytes, uint64_t stream,
                      int phases = 3);   // measurements only: 1 = clear + scan, 2 = pack of a block just scanned
+// K-11 powder statistics (csrc/powder.hip): ADDS up to kMaxFrames float32 frames of n elements into the
+// planar accumulators cnt int32 / sum int64 / sq int64 / qmax int32 / above int32 [nc, n] and nfr int64
+// [nc]: samples with vmin <= v <= vmax, quantised as q = rintf(v * 2^frac_bits).  nc == 2: keys (int32
+// [F] on the device) puts frame f into class 1 iff keys[f] >= key_min; nc == 1: keys == 0.  Never
+// clears (the caller sets qmax to INT32_MIN once); one owner thread per pixel, so two launches in
+// flight must not share accumulators.
+void launch_powder(const FramePtrs& fp, int nframes, int64_t n, float vmin, float vmax, int frac_bits,
+                   float thr_above, int nc, uint64_t keys, int key_min, uint64_t nfr, uint64_t cnt, uint64_t sum,
+                   uint64_t sq, uint64_t qmax, uint64_t above, uint64_t stream);
 }  // namespace pr

@@ -11,10 +11,12 @@ zero-copy leased batches), ``radial`` (on-GPU K-08 azimuthal integration: per-fr
 and an exact integer run accumulator), ``dark`` (on-GPU K-09 dark-run statistics of a RAW queue:
 per-pixel integer count / sum / sum of squares per gain candidate), ``sparse`` (on-GPU K-10 zero
 suppression: the pixels inside a value window as (index, value) pairs, optionally only of frames with
-at least ``--min_peaks`` peaks) or ``none``.  ``--out`` writes the peak lists / the radial accumulator /
-the dark statistics / the sparse frames to an ``.npz`` (several consumers' radial files add with
-``psana_ray_amd.radial.merge``, dark files with ``psana_ray_amd.dark.merge``, sparse files join with
-``psana_ray_amd.sparse.merge``).
+at least ``--min_peaks`` peaks), ``powder`` (on-GPU K-11 powder statistics: exact per-pixel run sum,
+spread, maximum and count above a threshold of the calibrated frames, misses and hits apart with
+``--min_peaks``) or ``none``.  ``--out`` writes the peak lists / the radial accumulator / the dark
+statistics / the sparse frames / the powder statistics to an ``.npz`` (several consumers' radial files add
+with ``psana_ray_amd.radial.merge``, dark files with ``psana_ray_amd.dark.merge``, sparse files join with
+``psana_ray_amd.sparse.merge``, powder files merge with ``psana_ray_amd.powder.merge``).
 """
 from __future__ import annotations
 
@@ -39,11 +41,12 @@ def build_parser():
     ap.add_argument("--ray_namespace", type=str, default=DEFAULT_RAY_NAMESPACE)
     ap.add_argument("--queue_name", type=str, default=DEFAULT_QUEUE_NAME)
     ap.add_argument("--device", type=str, default=None)
-    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "train", "none"],
+    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "train", "none"],
                     help="train: online PeakNetLite training from peak-finder labels (trainer.py); radial: radial "
                          "profile I(r) / I(q) of every frame + run accumulator (--nbins ... --radial_mask); dark: "
                          "per-pixel dark-run statistics of a RAW queue (--adu_min / --adu_max); sparse: zero-suppressed "
-                         "frames to disk (--sparse_thr ... --min_peaks)")
+                         "frames to disk (--sparse_thr ... --min_peaks); powder: per-pixel run sums / spread / max of the "
+                         "calibrated frames, misses and hits apart (--powder_vmin ... --min_peaks)")
     ap.add_argument("--lr", type=float, default=1e-3, help="--task train: AdamW learning rate")
     ap.add_argument("--save", type=str, default=None, help="--task train: write the model state_dict here")
     ap.add_argument("--ddp", action="store_true",
@@ -61,7 +64,8 @@ def build_parser():
     ap.add_argument("--out", type=str, default=None,
                     help="write peaks (npz) when --task peakfind; the radial accumulator + per-frame profiles (npz) "
                          "when --task radial; the dark statistics (psana_ray_amd.dark.DarkStats npz) when --task dark; "
-                         "the sparse frames (psana_ray_amd.sparse.SparseFrames npz) when --task sparse")
+                         "the sparse frames (psana_ray_amd.sparse.SparseFrames npz) when --task sparse; the powder "
+                         "statistics (psana_ray_amd.powder.PowderStats npz) when --task powder")
     g = ap.add_argument_group("--task radial")
     g.add_argument("--nbins", type=int, default=512, help="radial bins (1 .. 4096)")
     g.add_argument("--center", type=str, default=None, help="beam centre Y,X in image pixels (default: image centre)")
@@ -80,6 +84,7 @@ def build_parser():
     g.add_argument("--adu_min", type=int, default=0, help="ADU window: samples below are ignored (default 0)")
     g.add_argument("--adu_max", type=int, default=65535, help="ADU window: samples above are ignored (default 65535)")
     add_sparse_arguments(ap)
+    add_powder_arguments(ap)
     ap.add_argument("--timeout", type=float, default=300.0)
     ap.add_argument("--metrics_interval", type=float, default=10.0, help="seconds between rate lines; 0 disables")
     ap.add_argument("--metrics_json", type=str, default=None, help="append per-interval metrics as JSON lines")
@@ -103,6 +108,21 @@ def add_sparse_arguments(ap):
     g.add_argument("--part_frames", type=int, default=0,
                    help="K > 0: write parts STEM.00000.npz, ... of at most K frames while running, instead of one "
                         "file at the end")
+
+
+def add_powder_arguments(ap):
+    """The flags of ``--task powder`` (the producer CLI's ``--consumer_task powder`` takes the same); the hit
+    filter is --min_peaks / --thr_peak / --son_min, as for ``--task sparse``."""
+    g = ap.add_argument_group("--task powder")
+    g.add_argument("--powder_vmin", type=float, default=-float(2 ** 20),
+                   help="value window: samples below are ignored (default -2^20)")
+    g.add_argument("--powder_vmax", type=float, default=float(2 ** 20),
+                   help="value window: samples above are ignored (default 2^20)")
+    g.add_argument("--powder_frac_bits", type=int, default=2,
+                   help="values are accumulated as round(v * 2^S), S in 0 .. 16 (default 2); max(|vmin|, |vmax|) * 2^S "
+                        "must stay below 2^31 and bounds the frames of a run (printed at start)")
+    g.add_argument("--powder_thr", type=float, default=20.0,
+                   help="count per pixel the samples with value >= thr (default 20.0, the peak finder's threshold)")
 
 
 def _init_data_parallel(device) -> int:
@@ -380,8 +400,8 @@ def load_sparse_mask(path, shape):
     return (mask != 0).astype(np.uint8).reshape(-1)
 
 
-def sparse_layout(reader, args):
-    """(detector name, layout, frame shape) of the frames --task sparse will see, or a ValueError."""
+def sparse_layout(reader, args, needs="zero suppression needs"):
+    """(detector name, layout, frame shape) of the frames --task sparse (or powder) will see, or a ValueError."""
     import torch
 
     det = (reader.session_meta or {}).get("detector") or {}
@@ -393,7 +413,7 @@ def sparse_layout(reader, args):
     shape = tuple(ring.frame_shape)
     layout = det.get("mode")
     if ring.dtype != torch.float32 or layout == "raw":
-        raise ValueError("the queue carries raw uint16 frames without a calibration recipe; zero suppression needs "
+        raise ValueError(f"the queue carries raw uint16 frames without a calibration recipe; {needs} "
                          "calibrated ones (a producer with --mode calib / image, or --calibrate_on_read)")
     if layout is None:
         layout = "calib" if len(shape) == 3 else "image"
@@ -429,6 +449,48 @@ def run_sparse(args, reader, stop, progress) -> int:
     m = cons.metrics()
     print(f"Consumer {cid} sparse: frames={cons.frames} stored={m['frames_stored']} skipped={m['frames_skipped']} "
           f"overflowed={m['frames_overflowed']} pixels={m['pixels_stored']}", flush=True)
+    return rc
+
+
+def run_powder(args, reader, stop, progress) -> int:
+    """--task powder: accumulate until the end of the stream; ``progress["n"]`` counts frames."""
+    from .config import PeakFinderParams
+    from .pipeline import PowderConsumer
+
+    cid = reader.consumer_id
+    if not _has_whole_frames(reader, "powder", "powder statistics"):
+        return 2
+    cal = reader.calibrator
+    try:
+        name, layout, shape = sparse_layout(reader, args, needs="powder statistics need")
+    except ValueError as e:
+        log.error("--task powder: %s", e)
+        return 2
+    if not name:
+        log.error("--task powder: the session does not name its detector; pass --detector_name")
+        return 2
+    try:
+        cons = PowderConsumer(reader.endpoint, shape, vmin=args.powder_vmin, vmax=args.powder_vmax,
+                              frac_bits=args.powder_frac_bits, thr_above=args.powder_thr, min_peaks=args.min_peaks,
+                              peak_params=PeakFinderParams(thr_peak=args.thr_peak, son_min=args.son_min),
+                              detector=name, layout=layout, batch=args.batch, check_ring=cal is None)
+    except (ValueError, KeyError) as e:
+        log.error("--task powder: %s", e)
+        return 2
+    print(f"Consumer {cid} powder: max_frames={cons.max_frames} window=[{cons.vmin:g},{cons.vmax:g}] "
+          f"frac_bits={cons.frac_bits} thr={cons.thr_above:g} min_peaks={cons.min_peaks}", flush=True)
+    try:
+        rc = _drive(args, reader, stop, progress, cons,
+                    raw_meta=None if cal is None else lambda it: (it.rank, it.idx, it.gevt))
+    except ValueError as e:   # the run reached max_frames
+        log.error("--task powder: %s", e)
+        rc = 2
+    st = cons.stats()
+    fr = [int(f) for f in st.frames]
+    print(f"Consumer {cid} powder: frames={fr[0]}+{fr[1] if len(fr) > 1 else 0} detector={name} layout={layout} "
+          f"samples={int(st.cnt.sum())} above={int(st.above.sum())}", flush=True)
+    if args.out:
+        st.save(args.out)
     return rc
 
 
@@ -468,7 +530,7 @@ def main(argv=None) -> int:
         reporter = Reporter(registry, rank=cid if cid is not None else 0, interval=args.metrics_interval,
                             json_path=args.metrics_json).start()
         pf = None
-        run_task = {"radial": run_radial, "dark": run_dark, "sparse": run_sparse}.get(args.task)
+        run_task = {"radial": run_radial, "dark": run_dark, "sparse": run_sparse, "powder": run_powder}.get(args.task)
         if run_task is not None:   # the tasks that run a pipeline consumer to the end of the stream
             progress = {"n": 0}
             registry.register(args.task, lambda: {"frames_consumed": progress["n"]})

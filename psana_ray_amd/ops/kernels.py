@@ -1,4 +1,4 @@
-"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-10).
+"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-11).
 
 Every wrapper checks device / dtype / shape / contiguity / alignment on the host BEFORE the
 launch (a mis-shaped launch of a hand-written kernel can fault the GPU), splits batches into
@@ -286,6 +286,68 @@ def dark_accumulate(frames: Sequence[torch.Tensor], kind: int, adu_lo: int, adu_
     s = _ext.stream_handle(stream)
     for a, b in _chunks(F):
         C.dark([_ptr(t) for t in frames[a:b]], n, kind, adu_lo, adu_hi, _ptr(cnt), _ptr(sum), _ptr(sq), s)
+
+
+def powder_accumulate(frames: Sequence[torch.Tensor], vmin: float, vmax: float, frac_bits: int, thr_above: float,
+                      nfr: torch.Tensor, cnt: torch.Tensor, sum: torch.Tensor, sq: torch.Tensor, qmax: torch.Tensor,
+                      above: torch.Tensor, keys: Optional[torch.Tensor] = None, key_min: int = 0,
+                      frames_so_far: int = 0, stream=None):
+    """K-11 powder statistics (csrc/powder.hip; contract: ops.reference.powder_accumulate_reference).
+    frames: F float32 tensors of n elements (any layout) on one GPU.  ADDS every sample with vmin <= v <=
+    vmax, quantised as q = round_half_even(v * 2^frac_bits), to the planar accumulators cnt int32 / sum
+    int64 / sq int64 / qmax int32 / above int32 [NC, n] and the frames per class to nfr int64 [NC], on
+    the frames' device.  NC = 2 iff ``keys`` (int32 [F] on the device) is given: frame f is class 1 iff
+    keys[f] >= key_min.  The caller initialises the accumulators once per run (zeros, qmax INT32_MIN) and
+    passes in ``frames_so_far`` the frames they already hold: a run holds at most
+    ops.reference.powder_max_frames(vmin, vmax, frac_bits) frames.  One thread owns a pixel and there
+    are no atomics: launches in flight on DIFFERENT streams must not share accumulators.  Everything is
+    checked here, before any launch."""
+    from .reference import validate_powder_params
+
+    what = "powder_accumulate"
+    lo, hi, S, thr, _Q, max_frames = validate_powder_params(vmin, vmax, frac_bits, thr_above, what)
+    F = len(frames)
+    try:
+        frames_so_far, key_min = operator.index(frames_so_far), operator.index(key_min)
+    except TypeError:
+        raise ValueError(f"{what}: frames_so_far and key_min must be integers") from None
+    if not -2 ** 31 <= key_min < 2 ** 31:
+        raise ValueError(f"{what}: key_min must fit an int32")
+    if frames_so_far < 0 or frames_so_far + F > max_frames:
+        raise ValueError(f"{what}: {frames_so_far} + {F} frames would take the run past max_frames = {max_frames} "
+                         "(the int32 count and the int64 sum of squares)")
+    if not isinstance(nfr, torch.Tensor) or nfr.dtype != torch.int64 or nfr.dim() != 1 or nfr.numel() not in (1, 2) \
+            or not nfr.is_contiguous() or nfr.data_ptr() % 8:
+        raise ValueError(f"{what}: nfr must be a contiguous int64 [NC] tensor, NC 1 or 2")
+    nc = nfr.numel()
+    if (keys is not None) != (nc == 2):
+        raise ValueError(f"{what}: keys are given iff there are 2 classes (NC = {nc})")
+    if F == 0:
+        return
+    if not isinstance(frames[0], torch.Tensor):
+        raise ValueError(f"{what}: frames must be tensors")
+    dev = frames[0].device
+    n = frames[0].numel()
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: frames on {dev}, expected a GPU")
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"{what}: frames must have 1 .. 2^31 - 1 elements")
+    _check_frames(frames, torch.float32, n, dev, f"{what} in")
+    if nfr.device != dev:
+        raise ValueError(f"{what}: nfr on {nfr.device}, expected {dev}")
+    for t, dt, name in ((cnt, torch.int32, "cnt"), (sum, torch.int64, "sum"), (sq, torch.int64, "sq"),
+                        (qmax, torch.int32, "qmax"), (above, torch.int32, "above")):
+        if not isinstance(t, torch.Tensor) or t.shape != (nc, n) or t.dtype != dt or t.device != dev \
+                or not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError(f"{what}: {name} must be a contiguous, 16-B aligned {dt} [{nc}, {n}] tensor on {dev}")
+    if keys is not None and (not isinstance(keys, torch.Tensor) or keys.dtype != torch.int32 or keys.shape != (F,)
+                             or keys.device != dev or not keys.is_contiguous()):
+        raise ValueError(f"{what}: keys must be a contiguous int32 [{F}] tensor on {dev}")
+    C = _ext.load()
+    s = _ext.stream_handle(stream)
+    for a, b in _chunks(F):
+        C.powder([_ptr(t) for t in frames[a:b]], n, lo, hi, S, thr, nc, 0 if keys is None else _ptr(keys[a:b]),
+                 key_min, _ptr(nfr), _ptr(cnt), _ptr(sum), _ptr(sq), _ptr(qmax), _ptr(above), s)
 
 
 # elements per chunk of the K-10 scan (csrc/kernels.h kSparseChunk): one directory entry per chunk

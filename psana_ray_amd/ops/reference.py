@@ -355,3 +355,99 @@ def sparsify_reference(frames: torch.Tensor, thr: float, vmax: float, cap: int, 
     pix = torch.cat(pix) if pix else torch.zeros(0, dtype=torch.int32)
     val = torch.cat(val) if val else torch.zeros(0, dtype=torch.float32)
     return nnz, flags, offs, pix, val
+
+
+# K-11 powder statistics: the defaults of the contract (docs/ARCHITECTURE.md, "Powder statistics")
+POWDER_VMIN = -float(2 ** 20)    # the K-08 window
+POWDER_VMAX = float(2 ** 20)
+POWDER_FRAC_BITS = 2
+POWDER_THR_ABOVE = 20.0          # the peak finder's and K-10's default threshold
+POWDER_QMAX_NONE = -2 ** 31      # qmax of a pixel without a sample (INT32_MIN)
+
+
+def _powder_q(lo: float, hi: float, frac_bits: int) -> int:
+    """Q = ceil(max(|vmin|, |vmax|) * 2^S) in Python integers (no |q| of a contributing sample exceeds it)."""
+    from fractions import Fraction
+
+    m = max(abs(Fraction(lo)), abs(Fraction(hi))) * (1 << frac_bits)
+    return -((-m.numerator) // m.denominator)
+
+
+def validate_powder_params(vmin, vmax, frac_bits, thr_above, what: str = "powder_accumulate"):
+    """(vmin, vmax, thr_above) as the float32 values the kernel sees, frac_bits as a Python int, Q and
+    the run bound max_frames = min(2^31 - 1, (2^63 - 1) // max(1, Q * Q)) -- or ValueError."""
+    try:
+        frac_bits = operator.index(frac_bits)
+    except TypeError:
+        raise ValueError(f"{what}: frac_bits must be an integer, got {frac_bits!r}") from None
+    try:
+        with np.errstate(over="ignore"):   # a double beyond the float32 range becomes inf and is refused
+            lo, hi, thr = float(np.float32(vmin)), float(np.float32(vmax)), float(np.float32(thr_above))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: the value window and thr_above must be numbers") from None
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"{what}: the value window must be finite, got [{vmin}, {vmax}]")
+    if not lo <= hi:
+        raise ValueError(f"{what}: empty value window [{vmin}, {vmax}]")
+    if not 0 <= frac_bits <= 16:
+        raise ValueError(f"{what}: frac_bits must be in [0, 16], got {frac_bits}")
+    if thr != thr:
+        raise ValueError(f"{what}: thr_above is NaN")
+    Q = _powder_q(lo, hi, frac_bits)
+    if Q >= 2 ** 31:
+        raise ValueError(f"{what}: max(|vmin|, |vmax|) * 2^frac_bits must stay below 2^31 (q and qmax are int32), "
+                         f"got {Q}")
+    return lo, hi, frac_bits, thr, Q, min(2 ** 31 - 1, (2 ** 63 - 1) // max(1, Q * Q))
+
+
+def powder_max_frames(vmin=POWDER_VMIN, vmax=POWDER_VMAX, frac_bits=POWDER_FRAC_BITS) -> int:
+    """Frames a powder run holds at most: the int32 count and the int64 sum of squares both fit."""
+    return validate_powder_params(vmin, vmax, frac_bits, 0.0, "powder_max_frames")[5]
+
+
+def powder_accumulate_reference(frames: torch.Tensor, vmin: float, vmax: float, frac_bits: int, thr_above: float,
+                                keys=None, key_min: int = 0):
+    """K-11 golden: per-pixel powder statistics by exact INTEGER accumulation.  ``frames``: [F, ...]
+    float32 (any frame layout of n elements).  Frame f is class 1 ("hit") iff ``keys`` (int32 [F]) is
+    given and keys[f] >= key_min, else class 0; NC = 2 with keys, 1 without.  A sample v contributes iff
+    vmin <= v <= vmax as float32 (NaN fails, +-inf is outside); it gives q = int64(round_half_even(v *
+    2^S)) and adds 1 to cnt[c, p], q to sum[c, p], q * q to sq[c, p], (v >= thr_above) to above[c, p] and
+    raises qmax[c, p] to q.  Returns (nfr int64 [NC], cnt int32 [NC, n], sum int64 [NC, n], sq int64
+    [NC, n], qmax int32 [NC, n] -- INT32_MIN where no sample --, above int32 [NC, n]) of these frames
+    alone."""
+    lo, hi, S, thr, _Q, max_frames = validate_powder_params(vmin, vmax, frac_bits, thr_above, "powder")
+    if frames.dtype != torch.float32:
+        raise ValueError(f"powder: frames must be float32, got {frames.dtype}")
+    F = int(frames.shape[0])
+    if F < 1:
+        raise ValueError("powder: no frames")
+    if F > max_frames:
+        raise ValueError(f"powder: {F} frames are more than the {max_frames} a run holds at these parameters")
+    x = frames.detach().cpu().reshape(F, -1)
+    n = x.shape[1]
+    if not 1 <= n < 2 ** 31:
+        raise ValueError("powder: frames must have 1 .. 2^31 - 1 elements")
+    cls = torch.zeros(F, dtype=torch.int64)
+    nc = 1
+    if keys is not None:
+        k = torch.as_tensor(np.asarray(keys.cpu() if isinstance(keys, torch.Tensor) else keys)).reshape(-1)
+        if k.dtype != torch.int32 or k.numel() != F:
+            raise ValueError(f"powder: keys must be int32 [{F}]")
+        cls = (k >= int(key_min)).to(torch.int64)
+        nc = 2
+    ok = (x >= lo) & (x <= hi)
+    q = torch.where(ok, torch.round(x * float(2 ** S)), torch.zeros_like(x)).to(torch.int64)
+    hot = ok & (x >= thr)
+    none = torch.full_like(q, POWDER_QMAX_NONE)
+    nfr, cnt, s, sq, qmax, above = [], [], [], [], [], []
+    for c in range(nc):
+        m = ok & (cls == c).unsqueeze(1)
+        mi = m.to(torch.int64)
+        nfr.append((cls == c).sum())
+        cnt.append(mi.sum(dim=0))
+        s.append((mi * q).sum(dim=0))
+        sq.append((mi * q * q).sum(dim=0))
+        qmax.append(torch.where(m, q, none).amax(dim=0))
+        above.append((hot & m).to(torch.int64).sum(dim=0))
+    return (torch.stack(nfr).to(torch.int64), torch.stack(cnt).to(torch.int32), torch.stack(s), torch.stack(sq),
+            torch.stack(qmax).to(torch.int32), torch.stack(above).to(torch.int32))

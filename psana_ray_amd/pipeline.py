@@ -15,7 +15,8 @@ Consumer: drains this rank's shard in batches and runs the on-GPU peak finder (K
 consumer stream, releasing slots stream-ordered (BASELINE config 5); RadialProfileConsumer runs the
 radial profile (K-08) the same way and keeps an exact integer run accumulator on the device;
 SparseFrameConsumer writes the pixels above a threshold as (index, value) pairs (K-10), optionally only
-of the frames the peak finder calls hits.
+of the frames the peak finder calls hits; PowderConsumer keeps the exact per-pixel run sums, spread and
+maximum of the calibrated frames (K-11), split into misses and hits by the same device-side filter.
 """
 from __future__ import annotations
 
@@ -1123,3 +1124,161 @@ class SparseFrameConsumer(_BatchConsumer):
             self._advance(keep=0)   # first pass issues the last data copies, second collects them
             self.sync_streams()
         return self.results
+
+
+class PowderConsumer(_BatchConsumer):
+    """Consumer engine: batches of leased slots -> K-11 powder statistics (csrc/powder.hip) ->
+    stream-ordered release.
+
+    Per run: per-pixel, per-class count / sum / sum of squares / maximum / count above ``thr_above`` of
+    the quantised calibrated value inside ``[vmin, vmax]`` -- integers, so the result is exact in any
+    frame order.  With ``min_peaks > 0`` the peak finder (K-07) runs first on the same stream and its
+    per-frame counts decide ON THE DEVICE whether a frame is a hit (class 1) or a miss (class 0); with
+    ``min_peaks == 0`` there is one class.  The kernel owns a pixel per launch and uses no atomics, so
+    every consumer stream has its OWN accumulator set; :meth:`synchronize` combines the sets on the
+    host (sums, and the maximum for ``qmax``)."""
+
+    name = "powder"
+
+    def __init__(self, endpoint: QueueEndpoint, frame_shape, vmin: Optional[float] = None, vmax: Optional[float] = None,
+                 frac_bits: Optional[int] = None, thr_above: Optional[float] = None, min_peaks: int = 0,
+                 peak_params: Optional[PeakFinderParams] = None, detector: str = "", layout: str = "calib",
+                 batch: Optional[int] = None, stream_kind: str = CONSUMER_STREAM_KIND,
+                 streams: int = CONSUMER_STREAMS, ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
+        """frame_shape: the shape of a (calibrated) frame.  check_ring=False: the queue carries RAW
+        frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
+        from .ops import reference as _ref
+
+        self.shape = tuple(int(s) for s in frame_shape)
+        self.n = int(np.prod(self.shape))
+        if not 1 <= self.n < 2 ** 31:
+            raise ValueError("powder: frames must have 1 .. 2^31 - 1 elements")
+        self.vmin, self.vmax, self.frac_bits, self.thr_above, _Q, self.max_frames = _ref.validate_powder_params(
+            _ref.POWDER_VMIN if vmin is None else vmin, _ref.POWDER_VMAX if vmax is None else vmax,
+            _ref.POWDER_FRAC_BITS if frac_bits is None else frac_bits,
+            _ref.POWDER_THR_ABOVE if thr_above is None else thr_above, "powder")
+        self.min_peaks = int(min_peaks)
+        if self.min_peaks < 0:
+            raise ValueError("powder: min_peaks must be >= 0")
+        self.nc = 2 if self.min_peaks > 0 else 1
+        self.peak_params = peak_params or PeakFinderParams()
+        if self.min_peaks > 0:
+            if len(self.shape) not in (2, 3):
+                raise ValueError(f"powder: the hit filter needs 2-D or 3-D frames, got {self.shape}")
+            if self.peak_params.radius not in (1, 2):
+                raise ValueError("powder: peak finder radius must be 1 or 2")
+            self._pf_shape = self.shape if len(self.shape) == 3 else (1, *self.shape)
+        self.detector, self.layout = str(detector), str(layout)
+        if check_ring:
+            if endpoint.ring.dtype != torch.float32:
+                raise ValueError(f"powder: the queue carries {endpoint.ring.dtype} frames, powder statistics need "
+                                 "calibrated float32 ones")
+            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
+                raise ValueError(f"powder: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        self._host = self._new_host()
+        if self.gpu:
+            dev, nc, n = self.device, self.nc, self.n
+            # one accumulator set per stream; set k is only ever touched by launches on stream k
+            self._acc = [(torch.zeros(nc, dtype=torch.int64, device=dev),
+                          torch.zeros((nc, n), dtype=torch.int32, device=dev),
+                          torch.zeros((nc, n), dtype=torch.int64, device=dev),
+                          torch.zeros((nc, n), dtype=torch.int64, device=dev),
+                          torch.full((nc, n), _ref.POWDER_QMAX_NONE, dtype=torch.int32, device=dev),
+                          torch.zeros((nc, n), dtype=torch.int32, device=dev))
+                         for _ in self.streams]
+            self._pf = None   # the hit filter's peak finder
+            if self.min_peaks > 0:
+                self._pf = _PeakBuffers(dev, self.peak_params, self._pf_shape, self.batch, self._nbuf,
+                                        len(self.streams))
+
+    def _new_host(self) -> dict:
+        from .ops.reference import POWDER_QMAX_NONE
+
+        nc, n = self.nc, self.n
+        return {"frames": np.zeros(nc, np.int64), "cnt": np.zeros((nc, n), np.int64),
+                "sum": np.zeros((nc, n), np.int64), "sq": np.zeros((nc, n), np.int64),
+                "qmax": np.full((nc, n), POWDER_QMAX_NONE, np.int32), "above": np.zeros((nc, n), np.int64)}
+
+    @staticmethod
+    def _combine(h: dict, nfr, cnt, s, sq, qmax, above):
+        h["frames"] += nfr
+        h["cnt"] += cnt.astype(np.int64)
+        h["sum"] += s
+        h["sq"] += sq
+        h["qmax"] = np.maximum(h["qmax"], qmax)
+        h["above"] += above.astype(np.int64)
+
+    def _check_bound(self, n: int):
+        if self.frames + n > self.max_frames:
+            raise ValueError(f"powder: {self.frames} + {n} frames would take the run past max_frames = "
+                             f"{self.max_frames} (the int32 count and the int64 sum of squares)")
+
+    def _check_batch(self, n):
+        if n > self.batch:
+            raise ValueError(f"powder: {n} frames in a batch of at most {self.batch}")
+        self._check_bound(n)
+
+    def _limit(self, n_max):
+        self._check_bound(1)   # before any lease
+        return max(1, min(n_max, self.max_frames - self.frames))
+
+    def _peak_dict(self) -> dict:
+        if self.min_peaks <= 0:
+            return {}
+        p = self.peak_params
+        return {"thr_peak": float(p.thr_peak), "son_min": float(p.son_min), "radius": float(p.radius)}
+
+    def _launch_slots(self, C, slots, b, k, st):
+        nfr, cnt, s, q, qmax, above = self._acc[k]
+        keys = 0
+        if self._pf is not None:
+            self._pf.launch_slots(C, self.ep, slots, b, k, st)
+            keys = int(self._pf.counts[b].data_ptr())
+        C.powder_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.vmin, self.vmax, self.frac_bits,
+                       self.thr_above, self.nc, keys, self.min_peaks, int(nfr.data_ptr()), int(cnt.data_ptr()),
+                       int(s.data_ptr()), int(q.data_ptr()), int(qmax.data_ptr()), int(above.data_ptr()),
+                       int(st.cuda_stream))
+
+    def _launch_tensors(self, frames, b, k, st):
+        n = len(frames)
+        nfr, cnt, s, q, qmax, above = self._acc[k]
+        keys = None
+        if self._pf is not None:
+            self._pf.launch_tensors(frames, b, k, st)
+            keys = self._pf.counts[b, :n]
+        kernels.powder_accumulate([t.reshape(-1) for t in frames], self.vmin, self.vmax, self.frac_bits,
+                                  self.thr_above, nfr, cnt, s, q, qmax, above, keys=keys, key_min=self.min_peaks,
+                                  frames_so_far=self.frames, stream=st)
+
+    def _reference(self, frames, meta):
+        from .ops import reference
+
+        x = torch.stack([t.reshape(-1) for t in frames])
+        keys = None
+        if self.min_peaks > 0:
+            pk, _ = reference.peakfind_reference(x.reshape(len(frames), *self._pf_shape), self.peak_params)
+            keys = torch.tensor([int(p.shape[0]) for p in pk], dtype=torch.int32)
+        out = reference.powder_accumulate_reference(x, self.vmin, self.vmax, self.frac_bits, self.thr_above,
+                                                    keys=keys, key_min=self.min_peaks)
+        self._combine(self._host, *(t.numpy() for t in out))
+
+    def synchronize(self):
+        """Wait for every batch and combine the per-stream accumulator sets on the host (exact).  Returns
+        the dict of ``frames`` int64 [NC], ``cnt`` / ``sum`` / ``sq`` / ``above`` int64 [NC, n] and
+        ``qmax`` int32 [NC, n]."""
+        if self.gpu:
+            self.sync_streams()
+            self._host = self._new_host()
+            for acc in self._acc:
+                self._combine(self._host, *(t.cpu().numpy() for t in acc))
+        return self._host
+
+    def stats(self):
+        """The (synchronised) run as a :class:`psana_ray_amd.powder.PowderStats`."""
+        from .powder import PowderStats
+
+        h = self.synchronize()
+        return PowderStats(self.detector, self.layout, self.shape, self.vmin, self.vmax, self.frac_bits,
+                           self.thr_above, self.min_peaks, self._peak_dict(), h["frames"].copy(), h["cnt"].copy(),
+                           h["sum"].copy(), h["sq"].copy(), h["above"].copy(), h["qmax"].copy())

@@ -77,12 +77,16 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--data_dir", type=str, default=None, help="raw-run files directory (or $PSANA_RAY_DATA)")
     g.add_argument("--chunk", type=int, default=64, help="frames per H2D copy / kernel launch (<= 64)")
     g.add_argument("--route", type=str, default="balanced", choices=["balanced", "local_first", "spread"])
-    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse"],
+    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder"],
                    help="also consume on every producer rank (co-located consumer, BASELINE config 5): the K-07 "
                         "peak finder, the K-08 radial profile (default binning of psana-ray-consumer), the K-09 "
                         "dark statistics (needs --mode raw; --out_dark writes the file), or the K-10 zero "
                         "suppression (--out_sparse writes the file; --sparse_thr ... --min_peaks as for "
-                        "psana-ray-consumer --task sparse)")
+                        "psana-ray-consumer --task sparse), or the K-11 powder statistics (--out_powder writes the "
+                        "file; --powder_vmin ... --min_peaks as for psana-ray-consumer --task powder)")
+    g.add_argument("--out_powder", type=str, default=None,
+                   help="--consumer_task powder: write the rank's powder statistics (psana_ray_amd.powder.PowderStats "
+                        ".npz) here")
     g.add_argument("--out_sparse", type=str, default=None,
                    help="--consumer_task sparse: write the rank's sparse frames (psana_ray_amd.sparse.SparseFrames "
                         ".npz) here")
@@ -114,9 +118,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "the SDMA engines (utils/runtime_env.py)")
     g.add_argument("--local", action="store_true",
                    help="single-process queue: no rendezvous; requires --consumer_task (no external consumers)")
-    from .consumer import add_sparse_arguments
+    from .consumer import add_powder_arguments, add_sparse_arguments
 
     add_sparse_arguments(parser)
+    add_powder_arguments(parser)
     return parser
 
 
@@ -246,8 +251,8 @@ def main(argv=None) -> int:
     from .models import RadialBinning, make_geometry
     from .models.detector import Mode
     from .parallel.launch import bind_numa_to_device, detect, device_for
-    from .pipeline import (DarkStatsConsumer, PeakFinderConsumer, ProducerPipeline, RadialProfileConsumer,
-                           SparseFrameConsumer)
+    from .pipeline import (DarkStatsConsumer, PeakFinderConsumer, PowderConsumer, ProducerPipeline,
+                           RadialProfileConsumer, SparseFrameConsumer)
     from .queue.endpoint import EndOfStream, QueueEndpoint
     from .queue.ring import FrameRing, physical_slots
     from .queue.session import QueueSession
@@ -280,14 +285,14 @@ def main(argv=None) -> int:
                       "or a co-located --consumer_task")
             return 2
         mode = Mode.raw   # frames travel raw; DataReader applies read_mode
-    if args.consumer_task in ("radial", "sparse") and (mode == Mode.raw or int(args.panel_shards) > 1):
+    if args.consumer_task in ("radial", "sparse", "powder") and (mode == Mode.raw or int(args.panel_shards) > 1):
         log.error("--consumer_task %s needs whole calibrated frames (not --mode raw / --panel_shards)",
                   args.consumer_task)
         return 2
     if args.consumer_task == "dark" and (mode != Mode.raw or int(args.panel_shards) > 1):
         log.error("--consumer_task dark needs whole raw frames (--mode raw, no --panel_shards)")
         return 2
-    for flag, task in (("out_sparse", "sparse"), ("out_dark", "dark")):
+    for flag, task in (("out_sparse", "sparse"), ("out_dark", "dark"), ("out_powder", "powder")):
         if getattr(args, flag) is not None and args.consumer_task != task:
             log.error("--%s belongs to --consumer_task %s", flag, task)
             return 2
@@ -412,7 +417,7 @@ def main(argv=None) -> int:
             # consumer thread, at the end of the stream), report(result or None, frames consumed) after the join
             each = None
 
-            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse merge)
+            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder merge)
                 root, ext = os.path.splitext(path)
                 return path if size == 1 else f"{root}.r{rank}{ext}"
 
@@ -464,6 +469,25 @@ def main(argv=None) -> int:
                           f"pixels={m.get('pixels_stored', 0)}", flush=True)
                     if swriter.paths:
                         log.info("Rank %d: sparse frames written to %s", rank, ", ".join(swriter.paths))
+            elif args.consumer_task == "powder":
+                try:
+                    cons = PowderConsumer(ep, frame_shape, vmin=args.powder_vmin, vmax=args.powder_vmax,
+                                          frac_bits=args.powder_frac_bits, thr_above=args.powder_thr,
+                                          min_peaks=args.min_peaks, detector=args.detector_name, layout=mode.value)
+                except ValueError as e:
+                    log.error("--consumer_task powder: %s", e)
+                    return 2
+                log.info("Rank %d: powder statistics: max_frames=%d", rank, cons.max_frames)
+                finish = cons.stats
+
+                def report(ps, consumed):
+                    fr = [0] if ps is None else [int(f) for f in ps.frames]
+                    print(f"Consumer {rank} powder: frames={fr[0]}+{fr[1] if len(fr) > 1 else 0} "
+                          f"samples={0 if ps is None else int(ps.cnt.sum())}", flush=True)
+                    if ps is not None and args.out_powder:
+                        path = rank_path(args.out_powder)
+                        ps.save(path)
+                        log.info("Rank %d: powder statistics written to %s", rank, path)
             else:
                 cons = PeakFinderConsumer(ep, frame_shape, PeakFinderParams())
                 finish = cons.synchronize
