@@ -19,6 +19,7 @@ namespace py = pybind11;
 
 #include "engine.h"
 #include "fabric.h"
+#include "fabric_policy.h"
 #include "lifecycle.h"
 #include "kernels.h"
 #include "streams.h"
@@ -573,6 +574,35 @@ PYBIND11_MODULE(_C, m) {
       .def_static("copy_grid_for", &pr::QueueFabric::copy_grid_for, py::arg("consumer_devices"), py::arg("device"),
                   py::arg("per_peer"))
       .def("links", &pr::QueueFabric::links);
+  // the fabric's two policies as functions of plain numbers (csrc/fabric_policy.h), for the tests
+  m.def(
+      "fabric_route",
+      [](int policy, const std::vector<int>& offers, const std::vector<int64_t>& avail, const std::vector<bool>& keeper,
+         const std::vector<bool>& may_starve, int64_t local_credit, int64_t n_ready, int rr) {
+        pr::check(keeper.size() == avail.size() && may_starve.size() == avail.size(), "fabric_route: size mismatch");
+        std::vector<pr::fabric_policy::RouteCand> c(avail.size());
+        for (size_t i = 0; i < c.size(); ++i) c[i] = {avail[i], keeper[i], may_starve[i]};
+        const auto r = pr::fabric_policy::route(policy, offers, c, local_credit, n_ready, rr,
+                                                pr::QueueFabric::kLocalSlack, pr::QueueFabric::kFeedLocalReady);
+        return py::make_tuple(r.local, r.assign, r.left, r.rr, r.local_credit);
+      },
+      py::arg("policy"), py::arg("offers"), py::arg("avail"), py::arg("keeper"), py::arg("may_starve"),
+      py::arg("local_credit"), py::arg("n_ready"), py::arg("rr"));
+  m.def(
+      "fabric_grant_shares",
+      [](int cb, const std::vector<int64_t>& backlog, const std::vector<int64_t>& outstanding, int prefetch,
+         int64_t held, int64_t free_slots) {
+        pr::check(cb > 0 && backlog.size() == outstanding.size(), "fabric_grant_shares: bad arguments");
+        const auto g = pr::fabric_policy::grant_wants(cb, backlog, outstanding, prefetch, held,
+                                                      pr::QueueFabric::kMinGrants);
+        // as grant_free_slots: the pool is asked for min(total, cb) slots and gives what is free
+        const int64_t k = std::max<int64_t>(0, std::min({g.total, (int64_t)cb, free_slots}));
+        std::vector<int64_t> share(backlog.size(), 0);
+        for (int i : pr::fabric_policy::grant_deal(g.want, (size_t)k)) ++share[(size_t)i];
+        return py::make_tuple(g.want, g.total, share);
+      },
+      py::arg("cb"), py::arg("backlog"), py::arg("outstanding"), py::arg("prefetch") = 0, py::arg("held") = 0,
+      py::arg("free_slots") = int64_t(1) << 30);
 
   py::class_<pr::PinnedBuffer>(m, "PinnedBuffer", py::buffer_protocol())
       .def(py::init<size_t>(), py::arg("bytes"))

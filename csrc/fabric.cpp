@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "fabric_policy.h"
 #include "kernels.h"
 #include "lifecycle.h"
 #include "streams.h"
@@ -136,6 +137,23 @@ SlotHeader header_of(const Notice& nt) {
   return hd;
 }
 
+// A CopyRuns block is filled run by run: a full block is launched before the next run goes in, the
+// rest by a last flush.  Both return the launches they made.
+int flush_copy_runs(CopyRuns& cr, int wgs, hipStream_t stream) {
+  if (cr.n == 0) return 0;
+  launch_copy_runs(cr, wgs, reinterpret_cast<uint64_t>(stream));
+  cr.n = 0;
+  return 1;
+}
+int add_copy_run(CopyRuns& cr, uint64_t src, uint64_t dst, int64_t n16, int wgs, hipStream_t stream) {
+  const int launches = cr.n == kMaxCopyRuns ? flush_copy_runs(cr, wgs, stream) : 0;
+  cr.src[cr.n] = src;
+  cr.dst[cr.n] = dst;
+  cr.n16[cr.n] = n16;
+  ++cr.n;
+  return launches;
+}
+
 }  // namespace
 
 // A peer that exited is either gone (ESRCH) or a zombie its parent has not reaped yet (state Z/X
@@ -252,6 +270,11 @@ struct QueueFabric::Link {
   ~Link() {
     if (seg != nullptr) munmap(seg, map_bytes);
   }
+  // producer: one more entry of the notice ring (the consumer sees it once n_head is stored)
+  void post(const Notice& nt) {
+    seg_notices(seg)[n_head % (uint64_t)n] = nt;
+    ++n_head;
+  }
   LinkStatus status() const {
     LinkStatus s;
     s.peer = peer;
@@ -293,7 +316,56 @@ struct QueueFabric::Batch {
   double t_issue = 0;
   std::vector<std::pair<int, int64_t>> ck;  // (frame of the batch, pinned checksum result index)
   bool direct = false;                      // calibrated straight into the consumer's slots (no copy)
+
+  // f(a, count) for every run of frames [a, a + count) whose slots are contiguous on both sides
+  // (this pool and the consumer's ring): one copy each
+  template <class F>
+  void for_each_run(const SlotPool& pool, uint64_t slot_bytes, F f) const {
+    const int n = (int)slots.size();
+    for (int a = 0, e = 0; a < n; a = e) {
+      e = a + 1;
+      while (e < n && pool.slot_ptr(slots[e]) == pool.slot_ptr(slots[e - 1]) + slot_bytes &&
+             link->remote[rslots[e]] == link->remote[rslots[e - 1]] + slot_bytes)
+        ++e;
+      f(a, e - a);
+    }
+  }
 };
+
+// What the phases of one pass hand to each other (consumer_pass / producer_pass fill them).
+struct QueueFabric::ConsumerPass {
+  double now = 0;
+  bool closing = false;
+  int64_t work = 0;
+  std::vector<std::pair<Link*, uint64_t>> tails;      // notices read: n_tail to store once returns are posted
+  std::vector<std::pair<Link*, Notice>> rejected;     // returned frames a producer refused
+};
+
+struct QueueFabric::ProducerPass {
+  double now = 0;
+  int policy = 0;
+  int64_t work = 0;
+  int64_t local_credit = 0;   // the own consumer's credit routing left over (counts as "other credit")
+};
+
+void QueueFabric::bump(int64_t FabricStats::*field, int64_t n) {
+  std::lock_guard<std::mutex> lk(mu_);
+  st_.*field += n;
+}
+
+QueueFabric::Link* QueueFabric::in_link(int64_t peer) {
+  for (auto& lp : links_)
+    if (!lp->outgoing && lp->peer == peer) return lp.get();
+  return nullptr;
+}
+
+// "some batch writes a ring on another GPU": L2 lines of peer memory need a system-scope release
+// (a consumer on THIS GPU reads through the same L2: nothing to write back)
+bool QueueFabric::writes_peer_gpu(const std::vector<Batch>& bs) const {
+  for (const Batch& b : bs)
+    if (b.link->consumer_device >= 0 && b.link->consumer_device != device_) return true;
+  return false;
+}
 
 QueueFabric::QueueFabric(SlotPool* pool, int64_t slot_bytes, int device, bool is_producer, bool is_consumer,
                          int policy, int64_t self_mid)
@@ -437,16 +509,14 @@ int64_t QueueFabric::direct_pass() {
 // fabric's copy stream waits for their calibration (the slots' ready events), a system-scope release
 // on every XCD writes back L2 lines of peer memory the calibration kernels left dirty, optional
 // checksums read the frames back from the consumer rings, and each link's batch gets a completion
-// event; step 3 notices the frames when it completes (or counts them lost if the consumer left).
+// event; retire_copies notices the frames when it completes (or counts them lost if the consumer left).
 void QueueFabric::issue_direct(std::vector<Batch>& db) {
   trace::Range tr("fabric.direct_dispatch");
   if (xstream_ == nullptr) xstream_ = acquire_stream(device_, xstream_kind_);
   std::vector<int> all;
   for (const Batch& b : db) all.insert(all.end(), b.slots.begin(), b.slots.end());
   pool_->begin_send_batch(all, reinterpret_cast<uint64_t>(xstream_));
-  bool peer_gpu = false;   // a ring on another GPU was written: write back L2 lines of peer memory
-  for (const Batch& b : db) peer_gpu |= b.link->consumer_device >= 0 && b.link->consumer_device != device_;
-  if (peer_gpu || (direct_fence_ & 1)) launch_release_fence(reinterpret_cast<uint64_t>(xstream_));
+  if (writes_peer_gpu(db) || (direct_fence_ & 1)) launch_release_fence(reinterpret_cast<uint64_t>(xstream_));
   if (direct_fence_ & 2) launch_acquire_fence(reinterpret_cast<uint64_t>(xstream_));
   int64_t n = 0;
   for (Batch& b : db) {
@@ -501,8 +571,7 @@ void QueueFabric::finish_checksums(Batch& b) {
   int64_t n = 0;
   for (const SlotHeader& h : b.hdrs) n += ck_tagged(h.aux) ? 1 : 0;
   b.ck.clear();
-  std::lock_guard<std::mutex> lk(mu_);
-  st_.frames_checksummed += n;
+  bump(&FabricStats::frames_checksummed, n);
 }
 
 // Test-only fault injection (PSANA_RAY_AMD_FAULT_CORRUPT=N): every N-th frame this producer sends to
@@ -519,8 +588,7 @@ void QueueFabric::inject_corruption(const Batch& b, uint64_t stream) {
     else
       hip_check(hipMemsetAsync(reinterpret_cast<void*>(dst), 0x5A, 16, reinterpret_cast<hipStream_t>(stream)),
                 "hipMemsetAsync (fault injection)");
-    std::lock_guard<std::mutex> lk(mu_);
-    ++st_.frames_corrupted;
+    bump(&FabricStats::frames_corrupted);
   }
 }
 
@@ -744,8 +812,7 @@ void QueueFabric::apply_ops() {
       for (auto& l : links_)
         if (l->peer == op.mid && !l->dead) {
           l->dead = true;
-          std::lock_guard<std::mutex> lk(mu_);
-          ++st_.peers_dead;
+          bump(&FabricStats::peers_dead);
         }
       continue;
     }
@@ -808,8 +875,7 @@ void QueueFabric::apply_ops() {
       l->keeper = keeper_;
     }
     links_.push_back(l);
-    std::lock_guard<std::mutex> lk(mu_);
-    ++st_.links_opened;
+    bump(&FabricStats::links_opened);
   }
 }
 
@@ -966,23 +1032,19 @@ bool QueueFabric::post_return(Link* pref, int slot, const SlotHeader& h) {
   to->ret[slot] = 1;
   ++to->returned;
   ++returns_pending_;
-  std::lock_guard<std::mutex> lk(mu_);
-  ++st_.frames_returned;
+  bump(&FabricStats::frames_returned);
   return true;
 }
 
 void QueueFabric::drop_returned(int slot) {
   pool_->release(slot, 0);
-  std::lock_guard<std::mutex> lk(mu_);
-  ++st_.frames_dropped;
+  bump(&FabricStats::frames_dropped);
 }
 
 // ---------------------------------------------------------------------------------------
-int64_t QueueFabric::consumer_pass(double now) {
-  int64_t work = 0;
-  const bool closing = consumer_closed_.load();
-  // 0. frames the reader took since the last pass: tell each producer (its budget counts them
-  //    until then -- queue_size is one logical bound)
+// Consumer pass, phase 1.  Frames the reader took since the last pass: tell each producer (its budget
+// counts them until then -- queue_size is one logical bound), with this shard's demand.
+void QueueFabric::publish_taken() {
   int64_t tk_local = 0, tk_remote = 0;
   for (int64_t o : pool_->take_got_origins()) {
     if (o < 0) {
@@ -990,11 +1052,7 @@ int64_t QueueFabric::consumer_pass(double now) {
       continue;
     }
     ++tk_remote;
-    for (auto& lp : links_)
-      if (!lp->outgoing && lp->peer == o) {
-        ++lp->taken;
-        break;
-      }
+    if (Link* l = in_link(o)) ++l->taken;
   }
   if (tk_local + tk_remote > 0) {
     std::lock_guard<std::mutex> lk(mu_);
@@ -1010,340 +1068,340 @@ int64_t QueueFabric::consumer_pass(double now) {
       lp->seg->taken.store(lp->taken, std::memory_order_release);
       lp->seg->consumer_published.store(1, std::memory_order_release);
     }
-  // 1. notices: frames (-> READY), unused grants, answers to returned frames.  n_tail is stored only
-  //    after the returns of this pass were posted (a closing consumer hands back every frame noticed
-  //    before a producer sees n_tail catch up and acknowledges the close)
-  std::vector<int> done_slots, ret_slots;
-  std::vector<SlotHeader> done_hdr;
-  std::vector<std::pair<Link*, uint64_t>> tails;
-  std::vector<std::pair<Link*, Notice>> rejected;
-  for (auto& lp : links_) {
-    Link& l = *lp;
-    if (l.outgoing || l.seg == nullptr) continue;
-    LinkSeg* s = l.seg;
-    if (!l.attached && s->producer_pid.load(std::memory_order_acquire) != 0) {
-      l.attached = true;
-      if (l.named) {   // both ends mapped it: nothing may outlive the two processes
-        shm_remove(l.name);
-        l.named = false;
-      }
-    }
-    // EOS / detach flags BEFORE the notice head: a producer releases them after its last notice
-    const bool eos_flag = s->producer_eos.load(std::memory_order_acquire) != 0;
-    const bool det_flag = s->producer_detached.load(std::memory_order_acquire) != 0;
-    const uint64_t h = s->n_head.load(std::memory_order_acquire);
-    if (l.n_tail < h) {
-      Notice* ns = seg_notices(s);
-      done_slots.clear();
-      ret_slots.clear();
-      done_hdr.clear();
-      int64_t reclaimed = 0;
-      for (; l.n_tail < h; ++l.n_tail) {
-        const Notice nt = ns[l.n_tail % (uint64_t)l.n];
-        check(nt.slot >= 0 && nt.slot < (int)l.owed.size(),
-              "QueueFabric: producer " + std::to_string(l.peer) + " answered a slot outside the ring");
-        if (nt.flags & (kNoticeReclaimed | kNoticeRejected)) {
-          check(l.ret[nt.slot], "QueueFabric: producer " + std::to_string(l.peer) +
-                                    " answered a frame that was not returned to it");
-          l.ret[nt.slot] = 0;
-          --l.returned;
-          --returns_pending_;
-          if (nt.flags & kNoticeReclaimed) {
-            pool_->release(nt.slot, 0);   // copied out by the producer: the slot is free again
-            ++reclaimed;
-          } else {
-            rejected.emplace_back(&l, nt);
-          }
-          continue;
-        }
-        check(l.owed[nt.slot], "QueueFabric: producer " + std::to_string(l.peer) + " answered a slot it was never granted");
-        l.owed[nt.slot] = 0;
-        --l.outstanding;
-        if (nt.flags & kNoticeReturned) {
-          ret_slots.push_back(nt.slot);
-        } else {
-          done_slots.push_back(nt.slot);
-          done_hdr.push_back(header_of(nt));
-        }
-      }
-      tails.emplace_back(&l, l.n_tail);
-      pool_->complete_recv_batch_from(done_slots, done_hdr, l.peer);
-      pool_->cancel_recv_batch(ret_slots);
-      l.frames += (int64_t)done_slots.size();
-      work += (int64_t)(done_slots.size() + ret_slots.size()) + reclaimed;
-      std::lock_guard<std::mutex> lk(mu_);
-      st_.frames_recv += (int64_t)done_slots.size();
-      st_.bytes_recv += (int64_t)done_slots.size() * slot_bytes_;
-      st_.grants_returned += (int64_t)ret_slots.size();
-    }
-    if (eos_flag) l.eos = true;
-    if (det_flag) l.detached = true;
-    if (l.attached && !l.dead && now - l.last_check > kPidCheckS) {
-      l.last_check = now;
-      if (!pid_alive(s->producer_pid.load(std::memory_order_acquire))) {
-        l.dead = true;
-        std::lock_guard<std::mutex> lk(mu_);
-        ++st_.peers_dead;
-      }
-    }
-    if ((l.dead || l.detached) && l.outstanding > 0) {
-      // the producer is gone: everything it still owed comes back (a dead process's copies
-      // cannot land any more; a detached one synchronised them before leaving)
-      std::vector<int> back;
-      for (size_t i = 0; i < l.owed.size(); ++i)
-        if (l.owed[i]) {
-          back.push_back((int)i);
-          l.owed[i] = 0;
-        }
-      pool_->cancel_recv_batch(back);
-      l.outstanding = 0;
-      std::lock_guard<std::mutex> lk(mu_);
-      st_.grants_reclaimed += (int64_t)back.size();
-      work += (int64_t)back.size();
-    }
-    if ((l.dead || l.detached) && l.returned > 0) {
-      // returned frames it never answered: try the other producers
-      for (size_t i = 0; i < l.ret.size(); ++i)
-        if (l.ret[i]) {
-          l.ret[i] = 0;
-          --l.returned;
-          --returns_pending_;
-          const SlotHeader hd = pool_->header((int)i);
-          if (!post_return(nullptr, (int)i, hd)) drop_returned((int)i);
-          ++work;
-        }
-    }
-    if ((l.dead || l.detached) && l.named) {
+}
+
+// Phase 2, per incoming link: attach, notices, EOS / detach, liveness, and what a producer that is
+// gone still owed.
+void QueueFabric::poll_in_link(Link& l, ConsumerPass& cp) {
+  LinkSeg* s = l.seg;
+  if (!l.attached && s->producer_pid.load(std::memory_order_acquire) != 0) {
+    l.attached = true;
+    if (l.named) {   // both ends mapped it: nothing may outlive the two processes
       shm_remove(l.name);
       l.named = false;
     }
   }
-  for (auto& r : rejected) {   // that producer posted EOS meanwhile: another one, or drop
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      ++st_.returns_rejected;
+  // EOS / detach flags BEFORE the notice head: a producer releases them after its last notice
+  const bool eos_flag = s->producer_eos.load(std::memory_order_acquire) != 0;
+  const bool det_flag = s->producer_detached.load(std::memory_order_acquire) != 0;
+  const uint64_t h = s->n_head.load(std::memory_order_acquire);
+  if (l.n_tail < h) read_notices(l, h, cp);
+  if (eos_flag) l.eos = true;
+  if (det_flag) l.detached = true;
+  if (l.attached && !l.dead && cp.now - l.last_check > kPidCheckS) {
+    l.last_check = cp.now;
+    if (!pid_alive(s->producer_pid.load(std::memory_order_acquire))) {
+      l.dead = true;
+      bump(&FabricStats::peers_dead);
     }
+  }
+  if (l.dead || l.detached) reclaim_from_gone_producer(l, cp);
+}
+
+// Notices [n_tail, h) of one link: frames (-> READY), unused grants, answers to returned frames.
+void QueueFabric::read_notices(Link& l, uint64_t h, ConsumerPass& cp) {
+  const Notice* ns = seg_notices(l.seg);
+  std::vector<int> done_slots, ret_slots;
+  std::vector<SlotHeader> done_hdr;
+  int64_t reclaimed = 0;
+  for (; l.n_tail < h; ++l.n_tail) {
+    const Notice nt = ns[l.n_tail % (uint64_t)l.n];
+    check(nt.slot >= 0 && nt.slot < (int)l.owed.size(),
+          "QueueFabric: producer " + std::to_string(l.peer) + " answered a slot outside the ring");
+    if (nt.flags & (kNoticeReclaimed | kNoticeRejected)) {
+      check(l.ret[nt.slot], "QueueFabric: producer " + std::to_string(l.peer) +
+                                " answered a frame that was not returned to it");
+      l.ret[nt.slot] = 0;
+      --l.returned;
+      --returns_pending_;
+      if (nt.flags & kNoticeReclaimed) {
+        pool_->release(nt.slot, 0);   // copied out by the producer: the slot is free again
+        ++reclaimed;
+      } else {
+        cp.rejected.emplace_back(&l, nt);
+      }
+      continue;
+    }
+    check(l.owed[nt.slot], "QueueFabric: producer " + std::to_string(l.peer) + " answered a slot it was never granted");
+    l.owed[nt.slot] = 0;
+    --l.outstanding;
+    if (nt.flags & kNoticeReturned) {
+      ret_slots.push_back(nt.slot);
+    } else {
+      done_slots.push_back(nt.slot);
+      done_hdr.push_back(header_of(nt));
+    }
+  }
+  cp.tails.emplace_back(&l, l.n_tail);
+  pool_->complete_recv_batch_from(done_slots, done_hdr, l.peer);
+  pool_->cancel_recv_batch(ret_slots);
+  l.frames += (int64_t)done_slots.size();
+  cp.work += (int64_t)(done_slots.size() + ret_slots.size()) + reclaimed;
+  std::lock_guard<std::mutex> lk(mu_);
+  st_.frames_recv += (int64_t)done_slots.size();
+  st_.bytes_recv += (int64_t)done_slots.size() * slot_bytes_;
+  st_.grants_returned += (int64_t)ret_slots.size();
+}
+
+// The producer of `l` died or detached: its grants and the returns it never answered come back.
+void QueueFabric::reclaim_from_gone_producer(Link& l, ConsumerPass& cp) {
+  if (l.outstanding > 0) {
+    // everything it still owed comes back (a dead process's copies cannot land any more; a
+    // detached one synchronised them before leaving)
+    std::vector<int> back;
+    for (size_t i = 0; i < l.owed.size(); ++i)
+      if (l.owed[i]) {
+        back.push_back((int)i);
+        l.owed[i] = 0;
+      }
+    pool_->cancel_recv_batch(back);
+    l.outstanding = 0;
+    bump(&FabricStats::grants_reclaimed, (int64_t)back.size());
+    cp.work += (int64_t)back.size();
+  }
+  if (l.returned > 0) {
+    // returned frames it never answered: try the other producers
+    for (size_t i = 0; i < l.ret.size(); ++i)
+      if (l.ret[i]) {
+        l.ret[i] = 0;
+        --l.returned;
+        --returns_pending_;
+        const SlotHeader hd = pool_->header((int)i);
+        if (!post_return(nullptr, (int)i, hd)) drop_returned((int)i);
+        ++cp.work;
+      }
+  }
+  if (l.named) {
+    shm_remove(l.name);
+    l.named = false;
+  }
+}
+
+// Phase 3.  Returns a producer refused (it posted EOS meanwhile): another producer, or drop.
+void QueueFabric::reroute_rejected(ConsumerPass& cp) {
+  for (auto& r : cp.rejected) {
+    bump(&FabricStats::returns_rejected);
     r.first->eos = true;   // it will not accept more (its EOS flag follows)
     if (!post_return(nullptr, r.second.slot, header_of(r.second))) drop_returned(r.second.slot);
-    ++work;
+    ++cp.work;
   }
-  // 2. closing: hand every frame that arrived and was not taken back to a producer.  Once every live
-  //    producer confirmed it will notice no more frames (producer_seen_closed), nothing is ready
-  //    and every return was answered, `returns_final` tells the producers no return will follow:
-  //    only then may they acknowledge the close (a return can never reach a link whose producer
-  //    already let go of it)
-  if (closing) {
-    const std::vector<int> back = pool_->pop_ready_for_return(1 << 30);
-    for (int slot : back) {
-      const int64_t o = pool_->origin(slot);
-      Link* pref = nullptr;
-      for (auto& lp : links_)
-        if (!lp->outgoing && lp->peer == o) pref = lp.get();
-      if (!post_return(pref, slot, pool_->header(slot))) drop_returned(slot);
-      ++work;
-    }
+}
+
+// Phase 4 (closing).  Hand every frame that arrived and was not taken back to a producer.
+void QueueFabric::return_readahead(ConsumerPass& cp) {
+  const std::vector<int> back = pool_->pop_ready_for_return(1 << 30);
+  for (int slot : back) {
+    if (!post_return(in_link(pool_->origin(slot)), slot, pool_->header(slot))) drop_returned(slot);
+    ++cp.work;
   }
-  for (auto& t : tails) t.first->seg->n_tail.store(t.second, std::memory_order_release);
-  if (closing && !closed_posted_) {
+}
+
+// Phase 5 (closing).  consumer_closed into every mailbox; once every live producer confirmed it will
+// notice no more frames (producer_seen_closed), nothing is ready and every return was answered,
+// `returns_final` tells the producers no return will follow: only then may they acknowledge the
+// close (a return can never reach a link whose producer already let go of it).
+void QueueFabric::announce_close(ConsumerPass& cp) {
+  if (!closed_posted_) {
     for (auto& lp : links_)
       if (!lp->outgoing && lp->seg != nullptr) lp->seg->consumer_closed.store(1, std::memory_order_release);
     closed_posted_ = true;
   }
-  if (closing && closed_posted_ && !returns_final_ && returns_pending_ == 0 && pool_->n_ready() == 0) {
-    bool all_seen = true;
-    for (auto& lp : links_) {
-      const Link& l = *lp;
-      if (l.outgoing || l.seg == nullptr || !l.attached || l.dead || l.detached) continue;
-      if (l.seg->producer_seen_closed.load(std::memory_order_acquire) == 0 ||
-          l.seg->n_head.load(std::memory_order_acquire) != l.n_tail)
-        all_seen = false;
-    }
-    if (all_seen) {
-      for (auto& lp : links_)
-        if (!lp->outgoing && lp->seg != nullptr) lp->seg->returns_final.store(1, std::memory_order_release);
-      returns_final_ = true;
-      ++work;
-    }
+  if (returns_final_ || returns_pending_ != 0 || pool_->n_ready() != 0) return;
+  for (auto& lp : links_) {
+    const Link& l = *lp;
+    if (l.outgoing || l.seg == nullptr || !l.attached || l.dead || l.detached) continue;
+    if (l.seg->producer_seen_closed.load(std::memory_order_acquire) == 0 ||
+        l.seg->n_head.load(std::memory_order_acquire) != l.n_tail)
+      return;
   }
-  // 3. grants: free slots of this shard to the live producers that may still send, bounded by the
-  //    read-ahead allowance (prefetch - noticed-but-untaken - outstanding)
-  if (!closing) {
-    std::vector<Link*> act;
-    for (auto& lp : links_) {
-      Link* l = lp.get();
-      if (l->outgoing || !l->attached || l->eos || l->dead || l->detached) continue;
-      if (grant_filter_.load()) {
-        // queue keeper: producers that finished (draining), or live ones whose backlog nobody
-        // else can take (no other credit)
-        // (debounced: a consumer between two grant rounds holds no credit for a moment)
-        const bool listed = std::find(grantable_.begin(), grantable_.end(), l->peer) != grantable_.end();
-        const int64_t backlog = l->seg->producer_backlog.load(std::memory_order_relaxed);
-        const int64_t other = l->seg->producer_other_credit.load(std::memory_order_relaxed);
-        if (backlog > 0 && other <= 0) {
-          if (l->starved_since < 0) l->starved_since = now;
-        } else {
-          l->starved_since = -1;
-        }
-        const bool starved = l->starved_since >= 0 && now - l->starved_since >= kKeeperDebounceS;
-        if (!listed && !(backlog > 0 && starved)) continue;
-      }
-      act.push_back(l);
-    }
-    if (!act.empty()) {
-      const int cb = pool_->consumer_budget();
-      int64_t allowance = cb;
-      const int pf = prefetch_.load();
-      if (pf > 0) {
-        int64_t held = pool_->n_ready();
-        for (auto& lp : links_)
-          if (!lp->outgoing) held += lp->outstanding;
-        allowance = std::max<int64_t>(0, (int64_t)pf - held);
-      }
-      const int floor_g = std::max(kMinGrants, std::min(64, cb / (2 * (int)act.size())));
-      std::vector<int64_t> want(act.size());
-      int64_t total = 0;
-      for (size_t i = 0; i < act.size(); ++i) {
-        const int64_t backlog = std::max<int64_t>(0, act[i]->seg->producer_backlog.load(std::memory_order_relaxed));
-        want[i] = std::max<int64_t>(0, std::min<int64_t>(cb, floor_g + backlog) - act[i]->outstanding);
-        total += want[i];
-      }
-      total = std::min(total, allowance);
-      if (total > 0) {
-        const std::vector<int> slots = pool_->grant_batch((int)std::min<int64_t>(total, cb));
-        size_t k = 0;
-        std::vector<uint64_t> head(act.size());
-        for (size_t i = 0; i < act.size(); ++i) head[i] = act[i]->g_head;
-        // round-robin so concurrent demand shares the free slots
-        while (k < slots.size()) {
-          bool any = false;
-          for (size_t i = 0; i < act.size() && k < slots.size(); ++i) {
-            if (want[i] <= 0) continue;
-            Link& l = *act[i];
-            seg_grants(l.seg)[head[i] % (uint64_t)l.n] = slots[k];
-            l.owed[slots[k]] = 1;
-            ++l.outstanding;
-            ++head[i];
-            --want[i];
-            ++k;
-            any = true;
-          }
-          if (!any) break;
-        }
-        check(k == slots.size(), "QueueFabric: grant distribution left slots over");
-        for (size_t i = 0; i < act.size(); ++i)
-          if (head[i] != act[i]->g_head) {
-            act[i]->g_head = head[i];
-            act[i]->seg->g_head.store(head[i], std::memory_order_release);
-          }
-        work += (int64_t)slots.size();
-        std::lock_guard<std::mutex> lk(mu_);
-        st_.grants_given += (int64_t)slots.size();
-      }
-    }
-  }
-  // quiesced: no producer can still write into the ring and every returned frame was answered
-  // (close() waits for this before freeing the ring)
-  if (closing) {
-    bool q = returns_pending_ == 0 && returns_final_;
-    for (auto& lp : links_) {
-      const Link& l = *lp;
-      if (l.outgoing || l.seg == nullptr || !l.attached || l.dead || l.detached) continue;
-      if (l.seg->producer_ack_closed.load(std::memory_order_acquire) == 0) q = false;
-    }
-    quiesced_.store(q);
-  }
-  return work;
+  for (auto& lp : links_)
+    if (!lp->outgoing && lp->seg != nullptr) lp->seg->returns_final.store(1, std::memory_order_release);
+  returns_final_ = true;
+  ++cp.work;
 }
 
-int64_t QueueFabric::producer_pass(double now) {
-  int64_t work = 0;
-  const int policy = policy_.load();
-  auto post_notice = [&](Link& l, const Notice& nt) {
-    seg_notices(l.seg)[l.n_head % (uint64_t)l.n] = nt;
-    ++l.n_head;
-  };
-  // 1. attach / liveness / incoming grants, taken counters and returned frames
+// The live producers that may still send and that this consumer grants to.
+std::vector<QueueFabric::Link*> QueueFabric::grantable_producers(double now) {
+  std::vector<Link*> act;
   for (auto& lp : links_) {
-    Link& l = *lp;
-    if (!l.outgoing || l.dead) continue;
-    if (!l.attached) {
-      if (!try_attach(l, now)) continue;
-      ++work;
-    }
-    LinkSeg* s = l.seg;
-    if (now - l.last_check > kPidCheckS) {
-      l.last_check = now;
-      if (!pid_alive(s->consumer_pid)) {
-        l.dead = true;
-        std::lock_guard<std::mutex> lk(mu_);
-        ++st_.peers_dead;
+    Link* l = lp.get();
+    if (l->outgoing || !l->attached || l->eos || l->dead || l->detached) continue;
+    if (grant_filter_.load()) {
+      // queue keeper: producers that finished (draining), or live ones whose backlog nobody
+      // else can take (no other credit)
+      // (debounced: a consumer between two grant rounds holds no credit for a moment)
+      const bool listed = std::find(grantable_.begin(), grantable_.end(), l->peer) != grantable_.end();
+      const int64_t backlog = l->seg->producer_backlog.load(std::memory_order_relaxed);
+      const int64_t other = l->seg->producer_other_credit.load(std::memory_order_relaxed);
+      if (backlog > 0 && other <= 0) {
+        if (l->starved_since < 0) l->starved_since = now;
+      } else {
+        l->starved_since = -1;
       }
+      const bool starved = l->starved_since >= 0 && now - l->starved_since >= kKeeperDebounceS;
+      if (!listed && !(backlog > 0 && starved)) continue;
     }
-    if (l.dead) {
-      l.grants.clear();
-      l.returns.clear();
-      continue;
-    }
-    // returns first: a closing consumer posts them before consumer_closed
-    const uint64_t rh = s->r_head.load(std::memory_order_acquire);
-    if (l.r_tail < rh) {
-      const Notice* rs = seg_returns(s);
-      for (; l.r_tail < rh; ++l.r_tail) {
-        const Notice nt = rs[l.r_tail % (uint64_t)l.n];
-        check(nt.slot >= 0 && nt.slot < l.n, "QueueFabric: consumer " + std::to_string(l.peer) +
-                                                 " returned a slot outside its ring");
-        l.returns.push_back(nt);
-      }
-      s->r_tail.store(l.r_tail, std::memory_order_release);
-      ++work;
-    }
-    const uint64_t tk = s->taken.load(std::memory_order_acquire);
-    if (tk != l.taken_seen) {
-      l.taken_seen = tk;
-      ++work;
-    }
-    if (!l.closed && s->consumer_closed.load(std::memory_order_acquire) != 0) {
-      // from now on copies completing towards this link are requeued, never noticed
-      l.closed = true;
-      s->producer_seen_closed.store(1, std::memory_order_release);
-    }
-    if (l.closed) {
-      l.grants.clear();
-      continue;
-    }
-    const uint64_t h = s->g_head.load(std::memory_order_acquire);
-    if (l.g_tail < h) {
-      const int32_t* gs = seg_grants(s);
-      for (; l.g_tail < h; ++l.g_tail) {
-        const int32_t slot = gs[l.g_tail % (uint64_t)l.n];
-        check(slot >= 0 && slot < (int32_t)l.remote.size(),
-              "QueueFabric: consumer " + std::to_string(l.peer) + " granted a slot outside its ring");
-        l.grants.push_back(slot);
-      }
-      s->g_tail.store(l.g_tail, std::memory_order_release);
-      ++work;
-    }
-    if (l.eos_posted && !l.grants.empty()) {
-      // grants that raced with our EOS: hand them straight back (the consumer must not keep
-      // credit owed by a producer that will never send)
-      for (int slot : l.grants) post_notice(l, make_notice(slot, kNoticeReturned, SlotHeader{}));
-      {
-        std::lock_guard<std::mutex> lk(mu_);
-        st_.grants_returned += (int64_t)l.grants.size();
-      }
-      l.grants.clear();
-      s->n_head.store(l.n_head, std::memory_order_release);
+    act.push_back(l);
+  }
+  return act;
+}
+
+// Phase 5 (open).  Free slots of this shard to the live producers that may still send, bounded by
+// the read-ahead allowance (prefetch - noticed-but-untaken - outstanding); who gets how many is
+// fabric_policy's grant_wants / grant_deal.
+void QueueFabric::grant_free_slots(ConsumerPass& cp) {
+  const std::vector<Link*> act = grantable_producers(cp.now);
+  if (act.empty()) return;
+  const int cb = pool_->consumer_budget();
+  const int pf = prefetch_.load();
+  int64_t held = 0;
+  if (pf > 0) {
+    held = pool_->n_ready();
+    for (auto& lp : links_)
+      if (!lp->outgoing) held += lp->outstanding;
+  }
+  std::vector<int64_t> backlog(act.size()), outstanding(act.size());
+  for (size_t i = 0; i < act.size(); ++i) {
+    backlog[i] = act[i]->seg->producer_backlog.load(std::memory_order_relaxed);
+    outstanding[i] = act[i]->outstanding;
+  }
+  const fabric_policy::GrantWants g = fabric_policy::grant_wants(cb, backlog, outstanding, pf, held, kMinGrants);
+  if (g.total <= 0) return;
+  const std::vector<int> slots = pool_->grant_batch((int)std::min<int64_t>(g.total, cb));
+  const std::vector<int> to = fabric_policy::grant_deal(g.want, slots.size());
+  check(to.size() == slots.size(), "QueueFabric: grant distribution left slots over");
+  std::vector<uint8_t> got(act.size(), 0);
+  for (size_t k = 0; k < slots.size(); ++k) {
+    Link& l = *act[(size_t)to[k]];
+    seg_grants(l.seg)[l.g_head % (uint64_t)l.n] = slots[k];
+    l.owed[slots[k]] = 1;
+    ++l.outstanding;
+    ++l.g_head;
+    got[(size_t)to[k]] = 1;
+  }
+  for (size_t i = 0; i < act.size(); ++i)
+    if (got[i]) act[i]->seg->g_head.store(act[i]->g_head, std::memory_order_release);
+  cp.work += (int64_t)slots.size();
+  bump(&FabricStats::grants_given, (int64_t)slots.size());
+}
+
+// Phase 6 (closing).  Quiesced: no producer can still write into the ring and every returned frame
+// was answered (close() waits for this before freeing the ring).
+void QueueFabric::update_quiesced() {
+  bool q = returns_pending_ == 0 && returns_final_;
+  for (auto& lp : links_) {
+    const Link& l = *lp;
+    if (l.outgoing || l.seg == nullptr || !l.attached || l.dead || l.detached) continue;
+    if (l.seg->producer_ack_closed.load(std::memory_order_acquire) == 0) q = false;
+  }
+  quiesced_.store(q);
+}
+
+int64_t QueueFabric::consumer_pass(double now) {
+  ConsumerPass cp;
+  cp.now = now;
+  cp.closing = consumer_closed_.load();
+  publish_taken();
+  for (auto& lp : links_)
+    if (!lp->outgoing && lp->seg != nullptr) poll_in_link(*lp, cp);
+  reroute_rejected(cp);
+  if (cp.closing) return_readahead(cp);
+  // n_tail is stored only after the returns of this pass were posted (a closing consumer hands back
+  // every frame noticed before a producer sees n_tail catch up and acknowledges the close)
+  for (auto& t : cp.tails) t.first->seg->n_tail.store(t.second, std::memory_order_release);
+  if (cp.closing) {
+    announce_close(cp);
+  } else {
+    grant_free_slots(cp);
+  }
+  if (cp.closing) update_quiesced();
+  return cp.work;
+}
+
+// ---------------------------------------------------------------------------------------
+// Producer pass, phase 1, per outgoing link: attach, liveness, returned frames, taken counter,
+// consumer_closed, incoming grants (handed straight back once EOS is posted).
+void QueueFabric::poll_out_link(Link& l, ProducerPass& pp) {
+  if (!l.attached) {
+    if (!try_attach(l, pp.now)) return;
+    ++pp.work;
+  }
+  LinkSeg* s = l.seg;
+  if (pp.now - l.last_check > kPidCheckS) {
+    l.last_check = pp.now;
+    if (!pid_alive(s->consumer_pid)) {
+      l.dead = true;
+      bump(&FabricStats::peers_dead);
     }
   }
-  // 2. returned frames: copy them back into this pool (front of the FIFO), or refuse them after EOS
+  if (l.dead) {
+    l.grants.clear();
+    l.returns.clear();
+    return;
+  }
+  // returns first: a closing consumer posts them before consumer_closed
+  const uint64_t rh = s->r_head.load(std::memory_order_acquire);
+  if (l.r_tail < rh) {
+    const Notice* rs = seg_returns(s);
+    for (; l.r_tail < rh; ++l.r_tail) {
+      const Notice nt = rs[l.r_tail % (uint64_t)l.n];
+      check(nt.slot >= 0 && nt.slot < l.n, "QueueFabric: consumer " + std::to_string(l.peer) +
+                                               " returned a slot outside its ring");
+      l.returns.push_back(nt);
+    }
+    s->r_tail.store(l.r_tail, std::memory_order_release);
+    ++pp.work;
+  }
+  const uint64_t tk = s->taken.load(std::memory_order_acquire);
+  if (tk != l.taken_seen) {
+    l.taken_seen = tk;
+    ++pp.work;
+  }
+  if (!l.closed && s->consumer_closed.load(std::memory_order_acquire) != 0) {
+    // from now on copies completing towards this link are requeued, never noticed
+    l.closed = true;
+    s->producer_seen_closed.store(1, std::memory_order_release);
+  }
+  if (l.closed) {
+    l.grants.clear();
+    return;
+  }
+  const uint64_t h = s->g_head.load(std::memory_order_acquire);
+  if (l.g_tail < h) {
+    const int32_t* gs = seg_grants(s);
+    for (; l.g_tail < h; ++l.g_tail) {
+      const int32_t slot = gs[l.g_tail % (uint64_t)l.n];
+      check(slot >= 0 && slot < (int32_t)l.remote.size(),
+            "QueueFabric: consumer " + std::to_string(l.peer) + " granted a slot outside its ring");
+      l.grants.push_back(slot);
+    }
+    s->g_tail.store(l.g_tail, std::memory_order_release);
+    ++pp.work;
+  }
+  // grants that raced with our EOS: hand them straight back
+  if (l.eos_posted && !l.grants.empty()) return_unused_grants(l);
+}
+
+// The grants `l` holds go back unused (the consumer must not keep credit owed by a producer that
+// will never send).
+void QueueFabric::return_unused_grants(Link& l) {
+  for (int slot : l.grants) l.post(make_notice(slot, kNoticeReturned, SlotHeader{}));
+  bump(&FabricStats::grants_returned, (int64_t)l.grants.size());
+  l.grants.clear();
+  l.seg->n_head.store(l.n_head, std::memory_order_release);
+}
+
+// Phase 2.  Returned frames: copy them back into this pool (front of the FIFO), or refuse them
+// after EOS.
+void QueueFabric::reclaim_returns(ProducerPass& pp) {
   for (auto& lp : links_) {
     Link& l = *lp;
     if (!l.outgoing || l.dead || l.returns.empty()) continue;
     if (eos_any_) {
-      for (const Notice& nt : l.returns) post_notice(l, make_notice(nt.slot, kNoticeRejected, header_of(nt)));
+      for (const Notice& nt : l.returns) l.post(make_notice(nt.slot, kNoticeRejected, header_of(nt)));
       l.returns.clear();
       l.seg->n_head.store(l.n_head, std::memory_order_release);
-      ++work;
+      ++pp.work;
       continue;
     }
     const int want = (int)std::min<size_t>(l.returns.size(), 64);
@@ -1354,7 +1412,7 @@ int64_t QueueFabric::producer_pass(double now) {
     b.link = lp;
     b.slots = mine;
     b.stream = st;
-    b.t_issue = now;
+    b.t_issue = pp.now;
     for (size_t i = 0; i < mine.size(); ++i) {
       const Notice nt = l.returns.front();
       l.returns.pop_front();
@@ -1375,8 +1433,12 @@ int64_t QueueFabric::producer_pass(double now) {
     }
     l.reclaiming += (int)mine.size();
     reclaims_.push_back(std::move(b));
-    work += (int64_t)mine.size();
+    pp.work += (int64_t)mine.size();
   }
+}
+
+// Phase 3.  Reclaim copies that completed: the frames are queued again, the consumer's slots answered.
+void QueueFabric::retire_reclaims(ProducerPass& pp) {
   for (auto it = reclaims_.begin(); it != reclaims_.end();) {
     Batch& b = *it;
     if (b.ev != nullptr) {
@@ -1394,19 +1456,20 @@ int64_t QueueFabric::producer_pass(double now) {
     l.reclaiming -= n;
     l.noticed = std::max<int64_t>((int64_t)l.taken_seen, l.noticed - n);
     if (!l.dead) {
-      for (int i = 0; i < n; ++i) post_notice(l, make_notice(b.rslots[i], kNoticeReclaimed, b.hdrs[i]));
+      for (int i = 0; i < n; ++i) l.post(make_notice(b.rslots[i], kNoticeReclaimed, b.hdrs[i]));
       l.seg->n_head.store(l.n_head, std::memory_order_release);
     }
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      st_.frames_reclaimed += n;
-    }
+    bump(&FabricStats::frames_reclaimed, n);
     if (b.ev != nullptr) free_events_.push_back(b.ev);
     it = reclaims_.erase(it);
-    work += n;
+    pp.work += n;
   }
-  // 3. completed copies: notice the frames, or requeue them if their consumer left meanwhile.
-  //    Batches of one link complete in order (one stream per link); links are independent.
+}
+
+// Phase 4.  Completed copies: notice the frames, or requeue them if their consumer left meanwhile
+// (direct frames: copied back from a consumer that closed, lost with one that died).  Batches of
+// one link complete in order (one stream per link); links are independent.
+void QueueFabric::retire_copies(ProducerPass& pp) {
   std::vector<const Link*> blocked;
   for (auto it = inflight_.begin(); it != inflight_.end();) {
     Batch& b = *it;
@@ -1431,10 +1494,11 @@ int64_t QueueFabric::producer_pass(double now) {
     if (b.direct) d_inflight_.fetch_sub(n, std::memory_order_relaxed);   // noticed, copied back or lost
     if (l.attached && !l.dead && !l.closed) {
       finish_checksums(b);
-      for (int i = 0; i < n; ++i) post_notice(l, make_notice(b.rslots[i], 0, b.hdrs[i]));
+      for (int i = 0; i < n; ++i) l.post(make_notice(b.rslots[i], 0, b.hdrs[i]));
       l.seg->n_head.store(l.n_head, std::memory_order_release);
       // the copy is complete (host-observed): free the slots with no device wait, and count the
-      // frames as consumer read-ahead in the same locked step (step 5 recomputes the exact value)
+      // frames as consumer read-ahead in the same locked step (settle_out_links recomputes the
+      // exact value)
       const bool ext = !l.acked_close;
       pool_->end_send_completed(b.slots, ext);
       l.frames += n;
@@ -1442,38 +1506,18 @@ int64_t QueueFabric::producer_pass(double now) {
       std::lock_guard<std::mutex> lk(mu_);
       st_.frames_sent += n;
       st_.bytes_sent += (int64_t)n * slot_bytes_;
-      st_.copy_s += now - b.t_issue;
+      st_.copy_s += pp.now - b.t_issue;
     } else if (b.direct && l.closed && !l.dead && l.attached) {
-      // a consumer that CLOSED keeps its ring mapped until we acknowledge: copy the frames back
-      // into their local slots (still ours, SENDING) and requeue them at the FIFO front, like a
-      // copy that completed after the close (rare path: the fabric thread waits for it)
-      CopyRuns cr{};
-      cr.n = 0;
-      for (int i = 0; i < n; ++i) {
-        if (cr.n == kMaxCopyRuns) {
-          launch_copy_runs(cr, kLocalCopyWgs, reinterpret_cast<uint64_t>(xstream_));
-          cr.n = 0;
-        }
-        cr.src[cr.n] = l.remote[b.rslots[i]];
-        cr.dst[cr.n] = pool_->slot_ptr(b.slots[i]);
-        cr.n16[cr.n] = slot_bytes_ / 16;
-        ++cr.n;
-      }
-      if (cr.n > 0) launch_copy_runs(cr, kLocalCopyWgs, reinterpret_cast<uint64_t>(xstream_));
-      hip_check(hipStreamSynchronize(xstream_), "hipStreamSynchronize (direct frames back from a closed consumer)");
-      pool_->unsend_batch(b.slots);
-      std::lock_guard<std::mutex> lk(mu_);
-      st_.frames_requeued += n;
+      copy_back_direct(b);
+      bump(&FabricStats::frames_requeued, n);
     } else if (b.direct) {
       // the frame's data exists only in the ring of the consumer that died: lost (never noticed),
       // like the rest of that consumer's read-ahead
       pool_->end_send_completed(b.slots, false);
-      std::lock_guard<std::mutex> lk(mu_);
-      st_.frames_lost_direct += n;
+      bump(&FabricStats::frames_lost_direct, n);
     } else {
       pool_->unsend_batch(b.slots);
-      std::lock_guard<std::mutex> lk(mu_);
-      st_.frames_requeued += n;
+      bump(&FabricStats::frames_requeued, n);
     }
     if (b.ev != nullptr) free_events_.push_back(b.ev);
     if (b.grp != nullptr && --b.grp->pending == 0) {
@@ -1481,220 +1525,178 @@ int64_t QueueFabric::producer_pass(double now) {
       free_timed_.push_back(b.grp->end);
     }
     it = inflight_.erase(it);
-    work += n;
+    pp.work += n;
   }
-  // 4. route produced frames (FIFO) to this process's own consumer or to granted remote slots.
-  //    Keeper links are the last resort: a frame goes there only when no real consumer (and not
-  //    this process's own) has credit for it.
-  if (direct_on_) {
-    work += direct_pass();
-    // frames bound to a direct grant go to that grant's consumer, whatever the policy says now --
-    // every committed one, wherever it sits in the produced FIFO (behind a copy backlog longer than
-    // one pass's kMaxDispatch offers, a bound frame would hold its grant until the backlog drained,
-    // and a backlog that needs those grants would never drain)
-    std::vector<Batch> db;
-    {
-      std::lock_guard<std::mutex> lk(dmu_);
-      for (auto it = d_bound_.begin(); it != d_bound_.end();) {
-        if (pool_->state(it->first) != kProduced) {   // not committed yet
-          ++it;
-          continue;
-        }
-        Batch* b = nullptr;
-        for (Batch& x : db)
-          if (x.link == it->second.link) b = &x;
-        if (b == nullptr) {
-          db.emplace_back();
-          b = &db.back();
-          b->link = it->second.link;
-          b->t_issue = now;
-        }
-        b->slots.push_back(it->first);
-        b->rslots.push_back(it->second.rslot);
-        --it->second.link->direct;
-        it = d_bound_.erase(it);
-      }
-    }
-    if (!db.empty()) {
-      for (Batch& b : db) b.hdrs = pool_->headers(b.slots);
-      for (const Batch& b : db) work += (int64_t)b.slots.size();
-      issue_direct(db);
-    }
-  }
-  std::vector<int> offers = pool_->produced(kMaxDispatch);
-  if (direct_on_) {
-    // a frame bound after the scan above and committed before produced() is still in d_bound_ (the
-    // engine binds before it commits): never route it as a copy; the next pass issues it
+}
+
+// A consumer that CLOSED keeps its ring mapped until we acknowledge: copy the direct frames of `b`
+// back into their local slots (still ours, SENDING) and requeue them at the FIFO front, like a
+// copy that completed after the close (rare path: the fabric thread waits for it).
+void QueueFabric::copy_back_direct(const Batch& b) {
+  const Link& l = *b.link;
+  CopyRuns cr{};
+  cr.n = 0;
+  for (size_t i = 0; i < b.slots.size(); ++i)
+    add_copy_run(cr, l.remote[b.rslots[i]], pool_->slot_ptr(b.slots[i]), slot_bytes_ / 16, kLocalCopyWgs, xstream_);
+  flush_copy_runs(cr, kLocalCopyWgs, xstream_);
+  hip_check(hipStreamSynchronize(xstream_), "hipStreamSynchronize (direct frames back from a closed consumer)");
+  pool_->unsend_batch(b.slots);
+}
+
+// Phase 5 (direct on).  The offer pool, then the frames bound to a direct grant: they go to that
+// grant's consumer, whatever the policy says now -- every committed one, wherever it sits in the
+// produced FIFO (behind a copy backlog longer than one pass's kMaxDispatch offers, a bound frame
+// would hold its grant until the backlog drained, and a backlog that needs those grants would
+// never drain).
+void QueueFabric::issue_bound_direct(ProducerPass& pp) {
+  pp.work += direct_pass();
+  std::vector<Batch> db;
+  {
     std::lock_guard<std::mutex> lk(dmu_);
-    if (!d_bound_.empty()) {
-      std::vector<int> rest;
-      for (int sl : offers)
-        if (std::find_if(d_bound_.begin(), d_bound_.end(), [&](const auto& e) { return e.first == sl; }) == d_bound_.end())
-          rest.push_back(sl);
-      offers.swap(rest);
+    for (auto it = d_bound_.begin(); it != d_bound_.end();) {
+      if (pool_->state(it->first) != kProduced) {   // not committed yet
+        ++it;
+        continue;
+      }
+      Batch* b = nullptr;
+      for (Batch& x : db)
+        if (x.link == it->second.link) b = &x;
+      if (b == nullptr) {
+        db.emplace_back();
+        b = &db.back();
+        b->link = it->second.link;
+        b->t_issue = pp.now;
+      }
+      b->slots.push_back(it->first);
+      b->rslots.push_back(it->second.rslot);
+      --it->second.link->direct;
+      it = d_bound_.erase(it);
     }
   }
-  int64_t local_credit = (is_consumer_ && !consumer_closed_.load() && policy != 3) ? pool_->credits() : 0;
-  std::vector<Link*> cands;
+  if (db.empty()) return;
+  for (Batch& b : db) b.hdrs = pool_->headers(b.slots);
+  for (const Batch& b : db) pp.work += (int64_t)b.slots.size();
+  issue_direct(db);
+}
+
+// Up to kMaxDispatch produced frames (FIFO) for routing.
+std::vector<int> QueueFabric::take_offers() {
+  std::vector<int> offers = pool_->produced(kMaxDispatch);
+  if (!direct_on_) return offers;
+  // a frame bound after issue_bound_direct's scan and committed before produced() is still in
+  // d_bound_ (the engine binds before it commits): never route it as a copy; the next pass issues it
+  std::lock_guard<std::mutex> lk(dmu_);
+  if (d_bound_.empty()) return offers;
+  std::vector<int> rest;
+  for (int sl : offers)
+    if (std::find_if(d_bound_.begin(), d_bound_.end(), [&](const auto& e) { return e.first == sl; }) == d_bound_.end())
+      rest.push_back(sl);
+  return rest;
+}
+
+// Phase 6.  Route produced frames to this process's own consumer or to granted remote slots
+// (fabric_policy::route decides), then start their copies.  Leaves the own consumer's remaining
+// credit in pp.local_credit.
+void QueueFabric::route_produced(ProducerPass& pp) {
+  const std::vector<int> offers = take_offers();
+  pp.local_credit = (is_consumer_ && !consumer_closed_.load() && pp.policy != 3) ? pool_->credits() : 0;
+  std::vector<std::shared_ptr<Link>> cands;
   for (auto& lp : links_)
-    if (lp->outgoing && lp->attached && !lp->dead && !lp->closed && !lp->eos_posted) cands.push_back(lp.get());
-  if (policy == 4) {
+    if (lp->outgoing && lp->attached && !lp->dead && !lp->closed && !lp->eos_posted) cands.push_back(lp);
+  if (pp.policy == 4) {
     // remote_only: frames cross to another process whenever a remote consumer is linked
-    for (const Link* c : cands)
-      if (!c->keeper) local_credit = 0;
+    for (const auto& c : cands)
+      if (!c->keeper) pp.local_credit = 0;
   }
-  if (!offers.empty()) {
-    std::vector<int64_t> avail(cands.size());
-    for (size_t i = 0; i < cands.size(); ++i) avail[i] = (int64_t)cands[i]->grants.size();
-    if (policy == 2 && local_credit > 0) {
-      // spread: the own producer must not take the consumer credit that the remote producers'
-      // grants need.  A local route needs only credit, a grant needs a FREE slot whose release
-      // event has completed -- so without a reservation the local route wins every race and all
-      // frames stay local.  Keep each live remote producer's grant floor (consumer_pass) reserved.
-      std::vector<const Link*> in;
-      for (auto& lp : links_)
-        if (!lp->outgoing && lp->attached && !lp->eos && !lp->dead && !lp->detached) in.push_back(lp.get());
-      if (!in.empty()) {
-        const int cb = pool_->consumer_budget();
-        const int64_t floor_g = std::max(kMinGrants, std::min(64, cb / (2 * (int)in.size())));
-        int64_t reserve = 0;
-        for (const Link* l : in) reserve += std::max<int64_t>(0, floor_g - l->outstanding);
-        local_credit = std::max<int64_t>(0, local_credit - reserve);
-      }
-    }
-    std::vector<std::vector<int>> assign(cands.size());
-    std::vector<int> local;
-    const int K = (int)cands.size() + 1;   // position K-1 = this process's own consumer
-    // balanced: a remote consumer-ONLY member (no producer of its own feeds it) with NOTHING to
-    // read (its published ready count is 0) and credit here is starving -- competing consumers pull
-    // from one queue in the reference (shared_queue.py:19-24), so it is fed first while our own
-    // consumer has frames ready (a consumer-only rank next to a fast co-located consumer would
-    // otherwise never see a frame; BASELINE config 3).  Consumers that produce for themselves are
-    // left to their own producer, so the weak-scaling case stays local.  Each offer goes to the
-    // starving member given the fewest in this pass (several starving members share); a copy to it
-    // still in flight does not stop the feed (waiting for it idled the member one notice -> copy ->
-    // notice round trip per refill), its grants -- its read-ahead bound -- do.
-    std::vector<int> starving;
-    if (policy == 0 && (local_credit <= 0 || pool_->n_ready() >= kFeedLocalReady))
-      for (size_t i = 0; i < cands.size(); ++i)
-        // (a link whose consumer has not published its demand yet -- every field still the zero of a
-        // fresh mailbox -- is not starving: a self-fed prosumer would look like one)
-        if (!cands[i]->keeper && avail[i] > 0 && cands[i]->seg->consumer_published.load(std::memory_order_acquire) != 0 &&
-            cands[i]->seg->consumer_self_fed.load(std::memory_order_relaxed) == 0 &&
-            cands[i]->seg->consumer_ready.load(std::memory_order_relaxed) == 0)
-          starving.push_back((int)i);
-    for (int s : offers) {
-      int pick = -2;   // -2 none, -1 local, >= 0 remote
-      int sp = -1;
-      for (int i : starving)
-        if (avail[i] > 0 && (sp < 0 || assign[i].size() < assign[sp].size())) sp = i;
-      if (sp >= 0) {
-        assign[sp].push_back(s);
-        --avail[sp];
-        continue;
-      }
-      if (policy == 2) {
-        for (int t = 0; t < K && pick == -2; ++t) {
-          const int p = (rr_ + t) % K;
-          if (p == K - 1) {
-            if (local_credit > 0) pick = -1;
-          } else if (avail[p] > 0 && !cands[p]->keeper) {
-            pick = p;
-          }
-          if (pick != -2) rr_ = (p + 1) % K;
-        }
-      } else {
-        int best = -1;
-        for (size_t i = 0; i < cands.size(); ++i)
-          if (avail[i] > 0 && !cands[i]->keeper && (best < 0 || avail[i] > avail[best])) best = (int)i;
-        const int64_t best_n = best >= 0 ? avail[best] : 0;
-        if (local_credit > 0 && (policy == 1 || local_credit + kLocalSlack >= best_n)) pick = -1;
-        else if (best >= 0) pick = best;
-      }
-      if (pick == -2)   // nobody else: a keeper with credit
-        for (size_t i = 0; i < cands.size(); ++i)
-          if (avail[i] > 0 && cands[i]->keeper) {
-            pick = (int)i;
-            break;
-          }
-      if (pick == -2) break;
-      if (pick == -1) {
-        local.push_back(s);
-        --local_credit;
-      } else {
-        assign[pick].push_back(s);
-        --avail[pick];
-      }
-    }
-    for (int s : local) pool_->route_local(s);
-    if (!local.empty()) {
-      work += (int64_t)local.size();
-      std::lock_guard<std::mutex> lk(mu_);
-      st_.frames_local += (int64_t)local.size();
-    }
-    std::vector<Batch> kbatches;   // kernel engine: one dispatch for every link of this pass
-    for (size_t i = 0; i < cands.size(); ++i) {
-      if (assign[i].empty()) continue;
-      Link& l = *cands[i];
-      const std::vector<int>& slots = assign[i];
-      const int n = (int)slots.size();
-      Batch b;
-      for (std::shared_ptr<Link>& lp : links_)
-        if (lp.get() == &l) b.link = lp;
-      b.slots = slots;
-      b.hdrs = pool_->headers(slots);
-      b.rslots.assign(l.grants.begin(), l.grants.begin() + n);
-      l.grants.erase(l.grants.begin(), l.grants.begin() + n);
-      b.t_issue = now;
-      if (l.kcopy) {
-        l.inflight += n;
-        kbatches.push_back(std::move(b));
-        work += n;
-        continue;
-      }
-      if (device_ >= 0) {
-        trace::Range tr("fabric.copy_batch");
-        b.stream = l.stream != nullptr ? l.stream : stream_;
-        pool_->begin_send_batch(slots, reinterpret_cast<uint64_t>(b.stream));   // stream waits for the frames
-        start_checksums(b, reinterpret_cast<uint64_t>(b.stream));
-        int a = 0;
-        const uint64_t sb = (uint64_t)slot_bytes_;
-        while (a < n) {   // coalesce runs contiguous on both sides
-          int e = a + 1;
-          while (e < n && pool_->slot_ptr(slots[e]) == pool_->slot_ptr(slots[e - 1]) + sb &&
-                 l.remote[b.rslots[e]] == l.remote[b.rslots[e - 1]] + sb)
-            ++e;
-          hip_check(hipMemcpyAsync(reinterpret_cast<void*>(l.remote[b.rslots[a]]),
-                                   reinterpret_cast<const void*>(pool_->slot_ptr(slots[a])), (size_t)sb * (size_t)(e - a),
-                                   hipMemcpyDeviceToDevice, b.stream),
-                    "hipMemcpyAsync (frame -> consumer ring)");
-          a = e;
-        }
-        inject_corruption(b, reinterpret_cast<uint64_t>(b.stream));
-        b.ev = take_event();
-        hip_check(hipEventRecord(b.ev, b.stream), "hipEventRecord (frame copy)");
-      } else {
-        pool_->begin_send_batch(slots, 0);
-        start_checksums(b, 0);
-        for (int j = 0; j < n; ++j)
-          memcpy(reinterpret_cast<void*>(l.remote[b.rslots[j]]), reinterpret_cast<const void*>(pool_->slot_ptr(slots[j])),
-                 (size_t)slot_bytes_);
-        inject_corruption(b, 0);
-      }
-      l.inflight += n;
-      inflight_.push_back(std::move(b));
-      {
-        std::lock_guard<std::mutex> lk(mu_);
-        ++st_.batches;
-        ++st_.copy_launches;
-      }
-      work += n;
-    }
-    if (!kbatches.empty()) issue_copies(kbatches, now);
+  if (offers.empty()) return;
+  if (pp.policy == 2 && pp.local_credit > 0) {
+    // spread: keep each live remote producer's grant floor (grant_free_slots) reserved
+    std::vector<int64_t> outstanding;
+    for (auto& lp : links_)
+      if (!lp->outgoing && lp->attached && !lp->eos && !lp->dead && !lp->detached) outstanding.push_back(lp->outstanding);
+    if (!outstanding.empty())
+      pp.local_credit = std::max<int64_t>(
+          0, pp.local_credit - fabric_policy::spread_reserve(pool_->consumer_budget(), outstanding, kMinGrants));
   }
-  // 5. read-ahead accounting (frames noticed and not taken still count against this producer's
-  //    budget), demand hints, close acknowledgements, end of stream
-  int64_t readahead = 0, other_credit = local_credit;
+  const int64_t n_ready = (pp.policy == 0 && pp.local_credit > 0) ? pool_->n_ready() : 0;
+  std::vector<fabric_policy::RouteCand> rc(cands.size());
+  for (size_t i = 0; i < cands.size(); ++i) {
+    const Link& c = *cands[i];
+    rc[i].avail = (int64_t)c.grants.size();
+    rc[i].keeper = c.keeper;
+    // (a link whose consumer has not published its demand yet -- every field still the zero of a
+    // fresh mailbox -- is not starving: a self-fed prosumer would look like one)
+    rc[i].may_starve = pp.policy == 0 && !c.keeper && rc[i].avail > 0 &&
+                       c.seg->consumer_published.load(std::memory_order_acquire) != 0 &&
+                       c.seg->consumer_self_fed.load(std::memory_order_relaxed) == 0 &&
+                       c.seg->consumer_ready.load(std::memory_order_relaxed) == 0;
+  }
+  const fabric_policy::Routed r =
+      fabric_policy::route(pp.policy, offers, rc, pp.local_credit, n_ready, rr_, kLocalSlack, kFeedLocalReady);
+  rr_ = r.rr;
+  pp.local_credit = r.local_credit;
+  for (int s : r.local) pool_->route_local(s);
+  if (!r.local.empty()) {
+    pp.work += (int64_t)r.local.size();
+    bump(&FabricStats::frames_local, (int64_t)r.local.size());
+  }
+  std::vector<Batch> kbatches;   // kernel engine: one dispatch for every link of this pass
+  for (size_t i = 0; i < cands.size(); ++i)
+    if (!r.assign[i].empty()) send_routed(cands[i], r.assign[i], pp, kbatches);
+  if (!kbatches.empty()) issue_copies(kbatches, pp.now);
+}
+
+// The frames `slots` go to `lp`'s consumer, into the oldest grants it gave: a batch for this pass's
+// kernel dispatch (kbatches), or copied now by the runtime / the host.
+void QueueFabric::send_routed(const std::shared_ptr<Link>& lp, const std::vector<int>& slots, ProducerPass& pp,
+                              std::vector<Batch>& kbatches) {
+  Link& l = *lp;
+  const int n = (int)slots.size();
+  Batch b;
+  b.link = lp;
+  b.slots = slots;
+  b.hdrs = pool_->headers(slots);
+  b.rslots.assign(l.grants.begin(), l.grants.begin() + n);
+  l.grants.erase(l.grants.begin(), l.grants.begin() + n);
+  b.t_issue = pp.now;
+  l.inflight += n;
+  pp.work += n;
+  if (l.kcopy) {
+    kbatches.push_back(std::move(b));
+    return;
+  }
+  if (device_ >= 0) {
+    trace::Range tr("fabric.copy_batch");
+    b.stream = l.stream != nullptr ? l.stream : stream_;
+    pool_->begin_send_batch(slots, reinterpret_cast<uint64_t>(b.stream));   // stream waits for the frames
+    start_checksums(b, reinterpret_cast<uint64_t>(b.stream));
+    b.for_each_run(*pool_, (uint64_t)slot_bytes_, [&](int a, int count) {
+      hip_check(hipMemcpyAsync(reinterpret_cast<void*>(l.remote[b.rslots[a]]),
+                               reinterpret_cast<const void*>(pool_->slot_ptr(slots[a])),
+                               (size_t)slot_bytes_ * (size_t)count, hipMemcpyDeviceToDevice, b.stream),
+                "hipMemcpyAsync (frame -> consumer ring)");
+    });
+    inject_corruption(b, reinterpret_cast<uint64_t>(b.stream));
+    b.ev = take_event();
+    hip_check(hipEventRecord(b.ev, b.stream), "hipEventRecord (frame copy)");
+  } else {
+    pool_->begin_send_batch(slots, 0);
+    start_checksums(b, 0);
+    for (int j = 0; j < n; ++j)
+      memcpy(reinterpret_cast<void*>(l.remote[b.rslots[j]]), reinterpret_cast<const void*>(pool_->slot_ptr(slots[j])),
+             (size_t)slot_bytes_);
+    inject_corruption(b, 0);
+  }
+  inflight_.push_back(std::move(b));
+  std::lock_guard<std::mutex> lk(mu_);
+  ++st_.batches;
+  ++st_.copy_launches;
+}
+
+// Phase 7.  Read-ahead accounting (frames noticed and not taken still count against this
+// producer's budget), demand hints, close acknowledgements, end of stream.
+void QueueFabric::settle_out_links(ProducerPass& pp) {
+  int64_t readahead = 0, other_credit = pp.local_credit;
   bool returns_open = !reclaims_.empty();
   for (auto& lp : links_) {
     const Link& l = *lp;
@@ -1715,7 +1717,6 @@ int64_t QueueFabric::producer_pass(double now) {
     direct_idle = d_free_.empty() && d_taken_.empty() && d_bound_.empty() && d_cancel_.empty();
   }
   const bool all_routed = finished_.load() && backlog == 0 && inflight_.empty() && !returns_open && direct_idle;
-  bool drained = all_routed;
   for (auto& lp : links_) {
     Link& l = *lp;
     if (!l.outgoing || !l.attached) continue;
@@ -1739,28 +1740,42 @@ int64_t QueueFabric::producer_pass(double now) {
         shm_remove(l.name);
         if (s->kind == 0) shm_remove(std::string(s->ring_name));
       }
-      ++work;
+      ++pp.work;
     }
     if (all_routed && !l.dead && !l.closed && !l.eos_posted) {
       // give unused grants back, then EOS (released after the last notice)
-      for (int slot : l.grants) post_notice(l, make_notice(slot, kNoticeReturned, SlotHeader{}));
-      {
-        std::lock_guard<std::mutex> lk(mu_);
-        st_.grants_returned += (int64_t)l.grants.size();
-      }
-      l.grants.clear();
-      s->n_head.store(l.n_head, std::memory_order_release);
+      return_unused_grants(l);
       s->producer_eos.store(1, std::memory_order_release);
       l.eos_posted = true;
       l.eos = true;
       eos_any_ = true;
-      ++work;
+      ++pp.work;
     }
   }
   // links still being created by their consumer do not hold frames: EOS reaches them on attach
-  drained_.store(drained);
-  return work;
+  drained_.store(all_routed);
 }
+
+int64_t QueueFabric::producer_pass(double now) {
+  ProducerPass pp;
+  pp.now = now;
+  pp.policy = policy_.load();
+  // the links' state first: what completes below is noticed only to consumers still open now
+  for (auto& lp : links_)
+    if (lp->outgoing && !lp->dead) poll_out_link(*lp, pp);
+  reclaim_returns(pp);
+  retire_reclaims(pp);
+  retire_copies(pp);
+  // direct first: the offer pool refills and the bound frames leave before the copy path takes
+  // this pass's offers (take_offers skips what was bound since)
+  if (direct_on_) issue_bound_direct(pp);
+  route_produced(pp);
+  // last: it reads what routing left of the own consumer's credit (pp.local_credit), and posts EOS
+  // only after every notice of this pass
+  settle_out_links(pp);
+  return pp.work;
+}
+
 
 int QueueFabric::copy_grid_for(const std::vector<int>& consumer_devices, int device, int per_peer) {
   bool local = false;
@@ -1800,43 +1815,24 @@ void QueueFabric::issue_copies(std::vector<Batch>& kb, double now) {
   CopyRuns cr{};
   cr.n = 0;
   const uint64_t sb = (uint64_t)slot_bytes_;
-  int launches = 0;
   // grid: a copy inside this GPU's HBM (a consumer process on the same GPU) is bound by HBM and
   // takes kLocalCopyWgs workgroups; a copy over xGMI is bound by its point-to-point link (~150 GB/s),
   // so the grid grows by copy_wgs_ workgroups per distinct peer GPU this dispatch writes (7 links
   // out of an MI355X run concurrently) and leaves the other CUs to the calibration
   const int wgs = copy_grid(kb);
-  auto flush = [&] {
-    if (cr.n == 0) return;
-    launch_copy_runs(cr, wgs, reinterpret_cast<uint64_t>(xstream_));
-    cr.n = 0;
-    ++launches;
-  };
+  int launches = 0;
   for (const Batch& b : kb) {
-    const Link& l = *b.link;
     const int n = (int)b.slots.size();
-    int a = 0;
-    while (a < n) {   // coalesce runs contiguous on both sides
-      int e = a + 1;
-      while (e < n && pool_->slot_ptr(b.slots[e]) == pool_->slot_ptr(b.slots[e - 1]) + sb &&
-             l.remote[b.rslots[e]] == l.remote[b.rslots[e - 1]] + sb)
-        ++e;
-      if (cr.n == kMaxCopyRuns) flush();
-      cr.src[cr.n] = pool_->slot_ptr(b.slots[a]);
-      cr.dst[cr.n] = l.remote[b.rslots[a]];
-      cr.n16[cr.n] = (int64_t)(sb * (uint64_t)(e - a) / 16u);
-      ++cr.n;
-      a = e;
-    }
+    b.for_each_run(*pool_, sb, [&](int a, int count) {
+      launches += add_copy_run(cr, pool_->slot_ptr(b.slots[a]), b.link->remote[b.rslots[a]],
+                               (int64_t)(sb * (uint64_t)count / 16u), wgs, xstream_);
+    });
     g->frames += n;
     g->bytes += (int64_t)n * slot_bytes_;
   }
-  flush();
+  launches += flush_copy_runs(cr, wgs, xstream_);
   // another GPU's ring written: one system-scope release on every XCD before the completion signal
-  // (a consumer on THIS GPU reads through the same L2: nothing to write back)
-  bool peer_gpu = false;
-  for (const Batch& b : kb) peer_gpu |= b.link->consumer_device >= 0 && b.link->consumer_device != device_;
-  if (peer_gpu) launch_release_fence(reinterpret_cast<uint64_t>(xstream_));
+  if (writes_peer_gpu(kb)) launch_release_fence(reinterpret_cast<uint64_t>(xstream_));
   for (const Batch& b : kb) inject_corruption(b, reinterpret_cast<uint64_t>(xstream_));
   hip_check(hipEventRecord(g->end, xstream_), "hipEventRecord (copy end)");
   g->pending = (int)kb.size();

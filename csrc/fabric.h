@@ -294,11 +294,40 @@ class QueueFabric {
   struct Link;
   struct Batch;
   struct CopyGroup;   // one timed copy dispatch shared by the per-link batches it carries
+  struct ConsumerPass;   // what the phases of one pass hand to each other
+  struct ProducerPass;
   void loop();
   void fail(const std::string& msg);
+  void bump(int64_t FabricStats::*field, int64_t n = 1);   // one counter of st_, under mu_
   void apply_ops();
+  Link* in_link(int64_t peer);
+  // consumer pass and its phases, in order (who gets how many grants: fabric_policy.h)
   int64_t consumer_pass(double now);
+  void publish_taken();
+  void poll_in_link(Link& l, ConsumerPass& cp);
+  void read_notices(Link& l, uint64_t n_head, ConsumerPass& cp);
+  void reclaim_from_gone_producer(Link& l, ConsumerPass& cp);
+  void reroute_rejected(ConsumerPass& cp);
+  void return_readahead(ConsumerPass& cp);
+  void announce_close(ConsumerPass& cp);
+  std::vector<Link*> grantable_producers(double now);
+  void grant_free_slots(ConsumerPass& cp);
+  void update_quiesced();
+  // producer pass and its phases, in order (which consumer gets a frame: fabric_policy.h)
   int64_t producer_pass(double now);
+  void poll_out_link(Link& l, ProducerPass& pp);
+  void return_unused_grants(Link& l);
+  void reclaim_returns(ProducerPass& pp);
+  void retire_reclaims(ProducerPass& pp);
+  void retire_copies(ProducerPass& pp);
+  void copy_back_direct(const Batch& b);
+  void issue_bound_direct(ProducerPass& pp);
+  std::vector<int> take_offers();
+  void route_produced(ProducerPass& pp);
+  void send_routed(const std::shared_ptr<Link>& lp, const std::vector<int>& slots, ProducerPass& pp,
+                   std::vector<Batch>& kbatches);
+  void settle_out_links(ProducerPass& pp);
+  bool writes_peer_gpu(const std::vector<Batch>& bs) const;
   bool try_attach(Link& l, double now);
   void release_out_link(Link& l);
   void finish_in_link(Link& l);
