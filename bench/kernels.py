@@ -346,6 +346,73 @@ def main(argv=None):
                    {"classes_touched": touched, "rounds_us_per_frame": us(t_pw[k]),
                     "bytes_vs_read_floor": round(nbytes / (FR * npix * 4), 3),
                     "vs_read_floor": round(mp[0] / mr[0], 3), "TB_per_s": round(nbytes / mp[0] / 1e12, 3)}, frames=FR)
+    if want("hist"):
+        # K-12 per-pixel histograms: 64 SEPARATELY allocated float32 frames per launch, with the read floor
+        # and the powder kernel (one class) on the SAME frames in the same process -- alternating rounds, the
+        # median round of each.  Inputs are synthetic so that the accumulator traffic is known: "dark" is
+        # Gaussian around 0 with sigma = 2.0 (one bin of the default 64-bin window), "uniform" covers the
+        # window evenly (every line of the accumulator is touched: the worst flush).  Bytes: 4 B per pixel and
+        # frame plus a read and a write of every 128-B line of the accumulator that one launch touches
+        # (counted on the device after one launch into a cleared accumulator).  Every case runs in the three
+        # LDS layouts of the kernel: 0 = odd row pitch (the default), 1 = word-major, 2 = unpadded pitch.
+        from psana_ray_amd.ops.reference import (HIST_HI, HIST_LO, POWDER_FRAC_BITS, POWDER_QMAX_NONE, POWDER_THR_ABOVE,
+                                                 POWDER_VMAX, POWDER_VMIN)
+
+        FR, rounds = 64, 5
+        C = _ext.load()
+        gen = torch.Generator(device=dev).manual_seed(12)
+        inputs = {"dark": [torch.randn(npix, generator=gen, device=dev) * 2.0 for _ in range(FR)],
+                  "uniform": [HIST_LO + torch.rand(npix, generator=gen, device=dev) * (HIST_HI - HIST_LO)
+                              for _ in range(FR)]}
+        cases = [("64 bins, dark", "dark", 64), ("64 bins, uniform", "uniform", 64), ("256 bins, dark", "dark", 256)]
+        hists = {nb: torch.zeros((npix, nb), dtype=torch.int32, device=dev) for nb in (64, 256)}
+        touched = []
+        for _, inp, nb in cases:
+            h = hists[nb]
+            h.zero_()
+            kernels.pixel_hist(inputs[inp], HIST_LO, HIST_HI, nb, h)
+            torch.cuda.synchronize()
+            touched.append((int((h.view(-1, 32) != 0).any(dim=1).sum()) * 128, int((h.view(-1, 4) != 0).any(dim=1).sum()) * 16))
+        fp64 = [int(t.data_ptr()) for t in inputs["dark"]]
+        sums = torch.zeros(FR, dtype=torch.float32, device=dev)
+        pacc = (torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros((1, npix), dtype=torch.int32, device=dev),
+                torch.zeros((1, npix), dtype=torch.int64, device=dev), torch.zeros((1, npix), dtype=torch.int64, device=dev),
+                torch.full((1, npix), POWDER_QMAX_NONE, dtype=torch.int32, device=dev),
+                torch.zeros((1, npix), dtype=torch.int32, device=dev))
+
+        def hist_fn(k, layout):
+            _, inp, nb = cases[k]
+            return lambda: kernels.pixel_hist(inputs[inp], HIST_LO, HIST_HI, nb, hists[nb], _layout=layout)
+
+        layouts = (0, 1, 2)
+        t_read, t_pw, t_h = [], [], {(k, lay): [] for k in range(len(cases)) for lay in layouts}
+        for _ in range(rounds):
+            t_read.append(timeit(lambda: C.read_f32(fp64, npix, 16, False, int(sums.data_ptr()), _ext.stream_handle()),
+                                 a.iters))
+            for t, v in zip(pacc, (0, 0, 0, 0, POWDER_QMAX_NONE, 0)):   # every timed window starts a run
+                t.fill_(v)
+            t_pw.append(timeit(lambda: kernels.powder_accumulate(inputs["dark"], POWDER_VMIN, POWDER_VMAX, POWDER_FRAC_BITS,
+                                                                 POWDER_THR_ABOVE, *pacc), a.iters))
+            for key in t_h:
+                hists[cases[key[0]][2]].zero_()
+                t_h[key].append(timeit(hist_fn(*key), a.iters))
+        med = lambda ts: sorted(ts)[rounds // 2]   # noqa: E731
+        us = lambda ts: [round(t[0] * 1e6 / FR, 3) for t in ts]   # noqa: E731
+        mr, mp = med(t_read), med(t_pw)
+        fbytes = FR * npix * 4
+        report("read_f32 reference (K=16)", mr, fbytes, {"rounds_us_per_frame": us(t_read)}, frames=FR)
+        report("powder(NC=1)", mp, fbytes + npix * 56, {"rounds_us_per_frame": us(t_pw),
+                                                        "vs_read_floor": round(mp[0] / mr[0], 3)}, frames=FR)
+        for (k, lay), ts in t_h.items():
+            name, _, nb = cases[k]
+            mh = med(ts)
+            nbytes = fbytes + 2 * touched[k][0]
+            report(f"pixel_hist({name}, layout {lay})", mh, nbytes,
+                   {"nbins": nb, "lds_layout": lay, "rounds_us_per_frame": us(ts),
+                    "accumulator_bytes": npix * nb * 4, "lines_touched_bytes": touched[k][0],
+                    "chunks16_touched_bytes": touched[k][1], "bytes_vs_read_floor": round(nbytes / fbytes, 3),
+                    "vs_read_floor": round(mh[0] / mr[0], 3), "vs_powder": round(mh[0] / mp[0], 3),
+                    "TB_per_s": round(nbytes / mh[0] / 1e12, 3)}, frames=FR)
     if want("h2d"):
         C = _ext.load()
         hp = src.pool

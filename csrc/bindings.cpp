@@ -99,7 +99,7 @@ static FramePtrs make_ptrs(const std::vector<uint64_t>& in, const std::vector<ui
 }
 
 // The consumers' ring-slot bindings (peakfind_slots, radial_slots, dark_slots, sparsify_slots,
-// powder_slots): the two
+// powder_slots, pixel_hist_slots): the two
 // checks they share, then fn(index of the chunk's first slot, its slot pointers) for every chunk of at
 // most kMaxFrames slots.
 template <class Fn>
@@ -435,6 +435,28 @@ PYBIND11_MODULE(_C, m) {
         py::arg("frac_bits"), py::arg("thr_above"), py::arg("nc"), py::arg("keys"), py::arg("key_min"),
         py::arg("nfr"), py::arg("cnt"), py::arg("sum"), py::arg("sq"), py::arg("qmax"), py::arg("above"),
         py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+
+  m.def("pixel_hist",
+        [](const std::vector<uint64_t>& in, int64_t n, float lo, float hi, float inv_w, int nbins, uint64_t hist,
+           uint64_t stream, int layout) {
+          pr::launch_pixel_hist(make_ptrs(in, in), (int)in.size(), n, lo, hi, inv_w, nbins, hist, stream, layout);
+        },
+        py::arg("in_ptrs"), py::arg("n"), py::arg("lo"), py::arg("hi"), py::arg("inv_w"), py::arg("nbins"),
+        py::arg("hist"), py::arg("stream"), py::arg("layout") = 0,
+        "K-12 per-pixel histograms: adds up to 64 float32 frames into hist int32 [n, nbins]");
+  // consumer hot path: ring slots -> the histogram accumulator, one native call
+  m.def("pixel_hist_slots",
+        [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int64_t n, float lo, float hi,
+           float inv_w, int nbins, uint64_t hist, uint64_t stream) {
+          for_slot_chunks(pool, slot_bytes, slots, n * 4, "pixel_hist_slots", [&](int, const std::vector<uint64_t>& in) {
+            pr::launch_pixel_hist(make_ptrs(in, in), (int)in.size(), n, lo, hi, inv_w, nbins, hist, stream);
+          });
+        },
+        py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("n"), py::arg("lo"), py::arg("hi"),
+        py::arg("inv_w"), py::arg("nbins"), py::arg("hist"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("pixel_hist_tile_pixels", &pr::pixel_hist_tile_pixels, py::arg("nbins"),
+        "consecutive pixels one workgroup of the K-12 kernel owns at this nbins");
 
   m.def("copy_h2d_kernel",
         [](uint64_t dst, uint64_t src, int64_t bytes, int workgroups, uint64_t stream) {

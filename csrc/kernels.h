@@ -96,4 +96,14 @@ void launch_sparsify(const FramePtrs& fp, int nframes, int64_t n, float thr, flo
 void launch_powder(const FramePtrs& fp, int nframes, int64_t n, float vmin, float vmax, int frac_bits,
                    float thr_above, int nc, uint64_t keys, int key_min, uint64_t nfr, uint64_t cnt, uint64_t sum,
                    uint64_t sq, uint64_t qmax, uint64_t above, uint64_t stream);
+// K-12 per-pixel histograms (csrc/pixhist.hip): ADDS up to kMaxFrames float32 frames of n elements into
+// hist int32 [n, nbins] (pixel-major): a sample with lo <= v <= hi adds 1 to bin min(nbins - 1,
+// (int) floorf((v - lo) * inv_w)), inv_w = float32(nbins / (hi - lo)) from the caller.  n * nbins < 2^31.
+// Never clears; one owner workgroup per pixel, so two launches in flight must not share an accumulator.
+// pixel_hist_tile_pixels: the consecutive pixels one workgroup owns (a power of two, 64 .. 1024).
+constexpr int kHistMaxBins = 1024;
+int pixel_hist_tile_pixels(int nbins);
+void launch_pixel_hist(const FramePtrs& fp, int nframes, int64_t n, float lo, float hi, float inv_w, int nbins,
+                       uint64_t hist, uint64_t stream,
+                       int layout = 0);   // measurements only: 1 = word-major LDS tile, 2 = unpadded row pitch
 }  // namespace pr

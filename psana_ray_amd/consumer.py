@@ -13,10 +13,12 @@ per-pixel integer count / sum / sum of squares per gain candidate), ``sparse`` (
 suppression: the pixels inside a value window as (index, value) pairs, optionally only of frames with
 at least ``--min_peaks`` peaks), ``powder`` (on-GPU K-11 powder statistics: exact per-pixel run sum,
 spread, maximum and count above a threshold of the calibrated frames, misses and hits apart with
-``--min_peaks``) or ``none``.  ``--out`` writes the peak lists / the radial accumulator / the dark
+``--min_peaks``), ``hist`` (on-GPU K-12 per-pixel histograms: the exact spectrum of every pixel of the
+calibrated frames, for gain maps) or ``none``.  ``--out`` writes the peak lists / the radial accumulator / the dark
 statistics / the sparse frames / the powder statistics to an ``.npz`` (several consumers' radial files add
 with ``psana_ray_amd.radial.merge``, dark files with ``psana_ray_amd.dark.merge``, sparse files join with
-``psana_ray_amd.sparse.merge``, powder files merge with ``psana_ray_amd.powder.merge``).
+``psana_ray_amd.sparse.merge``, powder files merge with ``psana_ray_amd.powder.merge``, histogram files with
+``psana_ray_amd.hist.merge``).
 """
 from __future__ import annotations
 
@@ -41,12 +43,13 @@ def build_parser():
     ap.add_argument("--ray_namespace", type=str, default=DEFAULT_RAY_NAMESPACE)
     ap.add_argument("--queue_name", type=str, default=DEFAULT_QUEUE_NAME)
     ap.add_argument("--device", type=str, default=None)
-    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "train", "none"],
+    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "hist", "train", "none"],
                     help="train: online PeakNetLite training from peak-finder labels (trainer.py); radial: radial "
                          "profile I(r) / I(q) of every frame + run accumulator (--nbins ... --radial_mask); dark: "
                          "per-pixel dark-run statistics of a RAW queue (--adu_min / --adu_max); sparse: zero-suppressed "
                          "frames to disk (--sparse_thr ... --min_peaks); powder: per-pixel run sums / spread / max of the "
-                         "calibrated frames, misses and hits apart (--powder_vmin ... --min_peaks)")
+                         "calibrated frames, misses and hits apart (--powder_vmin ... --min_peaks); hist: per-pixel "
+                         "histograms of the calibrated frames (--hist_lo --hist_hi --hist_bins)")
     ap.add_argument("--lr", type=float, default=1e-3, help="--task train: AdamW learning rate")
     ap.add_argument("--save", type=str, default=None, help="--task train: write the model state_dict here")
     ap.add_argument("--ddp", action="store_true",
@@ -65,7 +68,8 @@ def build_parser():
                     help="write peaks (npz) when --task peakfind; the radial accumulator + per-frame profiles (npz) "
                          "when --task radial; the dark statistics (psana_ray_amd.dark.DarkStats npz) when --task dark; "
                          "the sparse frames (psana_ray_amd.sparse.SparseFrames npz) when --task sparse; the powder "
-                         "statistics (psana_ray_amd.powder.PowderStats npz) when --task powder")
+                         "statistics (psana_ray_amd.powder.PowderStats npz) when --task powder; the per-pixel histograms "
+                         "(psana_ray_amd.hist.PixelHist npz) when --task hist")
     g = ap.add_argument_group("--task radial")
     g.add_argument("--nbins", type=int, default=512, help="radial bins (1 .. 4096)")
     g.add_argument("--center", type=str, default=None, help="beam centre Y,X in image pixels (default: image centre)")
@@ -85,6 +89,7 @@ def build_parser():
     g.add_argument("--adu_max", type=int, default=65535, help="ADU window: samples above are ignored (default 65535)")
     add_sparse_arguments(ap)
     add_powder_arguments(ap)
+    add_hist_arguments(ap)
     ap.add_argument("--timeout", type=float, default=300.0)
     ap.add_argument("--metrics_interval", type=float, default=10.0, help="seconds between rate lines; 0 disables")
     ap.add_argument("--metrics_json", type=str, default=None, help="append per-interval metrics as JSON lines")
@@ -123,6 +128,16 @@ def add_powder_arguments(ap):
                         "must stay below 2^31 and bounds the frames of a run (printed at start)")
     g.add_argument("--powder_thr", type=float, default=20.0,
                    help="count per pixel the samples with value >= thr (default 20.0, the peak finder's threshold)")
+
+
+def add_hist_arguments(ap):
+    """The flags of ``--task hist`` (the producer CLI's ``--consumer_task hist`` takes the same)."""
+    g = ap.add_argument_group("--task hist")
+    g.add_argument("--hist_lo", type=float, default=-32.0, help="window: samples below are ignored (default -32)")
+    g.add_argument("--hist_hi", type=float, default=96.0, help="window: samples above are ignored (default 96)")
+    g.add_argument("--hist_bins", type=int, default=64,
+                   help="equal bins of [hist_lo, hist_hi], 1 .. 1024 (default 64: bins of 2.0); pixels x bins must "
+                        "stay below 2^31, and every consumer stream holds pixels x bins x 4 bytes on the device")
 
 
 def _init_data_parallel(device) -> int:
@@ -494,6 +509,44 @@ def run_powder(args, reader, stop, progress) -> int:
     return rc
 
 
+def run_hist(args, reader, stop, progress) -> int:
+    """--task hist: accumulate until the end of the stream; ``progress["n"]`` counts frames."""
+    from .pipeline import PixelHistConsumer
+
+    cid = reader.consumer_id
+    if not _has_whole_frames(reader, "hist", "pixel histograms"):
+        return 2
+    cal = reader.calibrator
+    try:
+        name, layout, shape = sparse_layout(reader, args, needs="pixel histograms need")
+    except ValueError as e:
+        log.error("--task hist: %s", e)
+        return 2
+    if not name:
+        log.error("--task hist: the session does not name its detector; pass --detector_name")
+        return 2
+    try:
+        cons = PixelHistConsumer(reader.endpoint, shape, lo=args.hist_lo, hi=args.hist_hi, nbins=args.hist_bins,
+                                 detector=name, layout=layout, batch=args.batch, check_ring=cal is None)
+    except (ValueError, KeyError) as e:
+        log.error("--task hist: %s", e)
+        return 2
+    print(f"Consumer {cid} hist: window=[{cons.lo:g},{cons.hi:g}] bins={cons.nbins} "
+          f"accumulator_bytes={cons.acc_bytes}", flush=True)
+    try:
+        rc = _drive(args, reader, stop, progress, cons,
+                    raw_meta=None if cal is None else lambda it: (it.rank, it.idx, it.gevt))
+    except ValueError as e:   # the run reached 2^31 - 1 frames
+        log.error("--task hist: %s", e)
+        rc = 2
+    ph = cons.stats()
+    print(f"Consumer {cid} hist: frames={ph.frames} detector={name} layout={layout} "
+          f"samples={int(ph.hist.sum(dtype='int64'))}", flush=True)
+    if args.out:
+        ph.save(args.out)
+    return rc
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=getattr(logging, args.log_level), format="%(asctime)s - %(levelname)s - %(message)s")
@@ -530,7 +583,8 @@ def main(argv=None) -> int:
         reporter = Reporter(registry, rank=cid if cid is not None else 0, interval=args.metrics_interval,
                             json_path=args.metrics_json).start()
         pf = None
-        run_task = {"radial": run_radial, "dark": run_dark, "sparse": run_sparse, "powder": run_powder}.get(args.task)
+        run_task = {"radial": run_radial, "dark": run_dark, "sparse": run_sparse, "powder": run_powder,
+                    "hist": run_hist}.get(args.task)
         if run_task is not None:   # the tasks that run a pipeline consumer to the end of the stream
             progress = {"n": 0}
             registry.register(args.task, lambda: {"frames_consumed": progress["n"]})

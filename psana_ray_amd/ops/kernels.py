@@ -1,4 +1,4 @@
-"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-11).
+"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-12).
 
 Every wrapper checks device / dtype / shape / contiguity / alignment on the host BEFORE the
 launch (a mis-shaped launch of a hand-written kernel can fault the GPU), splits batches into
@@ -348,6 +348,53 @@ def powder_accumulate(frames: Sequence[torch.Tensor], vmin: float, vmax: float, 
     for a, b in _chunks(F):
         C.powder([_ptr(t) for t in frames[a:b]], n, lo, hi, S, thr, nc, 0 if keys is None else _ptr(keys[a:b]),
                  key_min, _ptr(nfr), _ptr(cnt), _ptr(sum), _ptr(sq), _ptr(qmax), _ptr(above), s)
+
+
+def pixel_hist_tile_pixels(nbins: int) -> int:
+    """The consecutive pixels one workgroup of the K-12 kernel owns at ``nbins`` (a power of two, 64 .. 1024):
+    the sizes around it are where the kernel changes path."""
+    from .reference import validate_pixel_hist_params
+
+    return int(_ext.load().pixel_hist_tile_pixels(validate_pixel_hist_params(0.0, 1.0, nbins, what="pixel_hist_tile_pixels")[2]))
+
+
+def pixel_hist(frames: Sequence[torch.Tensor], lo: float, hi: float, nbins: int, hist: torch.Tensor,
+               frames_so_far: int = 0, stream=None, _layout: int = 0):
+    """K-12 per-pixel histograms (csrc/pixhist.hip; contract: ops.reference.pixel_hist_reference).
+    frames: F float32 tensors of n elements (any layout) on one GPU.  Every sample with lo <= v <= hi ADDS 1
+    to hist[p, min(nbins - 1, floor((v - lo) * inv_w))]; ``hist`` is a contiguous, 16-B aligned int32
+    [n, nbins] tensor on the frames' device that the caller zeroes once per run and whose frames so far it
+    passes in ``frames_so_far``: a run holds at most 2^31 - 1 frames.  One workgroup owns a pixel and there
+    are no global atomics: launches in flight on DIFFERENT streams must not share an accumulator.
+    Everything is checked here, before any launch.  ``_layout`` selects an LDS layout for measurements."""
+    from .reference import validate_pixel_hist_params
+
+    what = "pixel_hist"
+    F = len(frames)
+    flo, fhi, nbins, inv_w = validate_pixel_hist_params(lo, hi, nbins, frames_so_far=frames_so_far, frames=F, what=what)
+    if _layout not in (0, 1, 2):
+        raise ValueError(f"{what}: _layout must be 0, 1 or 2")
+    if not isinstance(hist, torch.Tensor) or hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[1] != nbins \
+            or not hist.is_contiguous() or hist.data_ptr() % 16:
+        raise ValueError(f"{what}: hist must be a contiguous, 16-B aligned int32 [n, {nbins}] tensor")
+    n = int(hist.shape[0])
+    validate_pixel_hist_params(lo, hi, nbins, n=n, what=what)
+    if F == 0:
+        return
+    if not isinstance(frames[0], torch.Tensor):
+        raise ValueError(f"{what}: frames must be tensors")
+    dev = frames[0].device
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: frames on {dev}, expected a GPU")
+    if frames[0].numel() != n:
+        raise ValueError(f"{what}: frames of {frames[0].numel()} elements for hist [{n}, {nbins}]")
+    _check_frames(frames, torch.float32, n, dev, f"{what} in")
+    if hist.device != dev:
+        raise ValueError(f"{what}: hist on {hist.device}, expected {dev}")
+    C = _ext.load()
+    s = _ext.stream_handle(stream)
+    for a, b in _chunks(F):
+        C.pixel_hist([_ptr(t) for t in frames[a:b]], n, flo, fhi, inv_w, nbins, _ptr(hist), s, _layout)
 
 
 # elements per chunk of the K-10 scan (csrc/kernels.h kSparseChunk): one directory entry per chunk

@@ -451,3 +451,80 @@ def powder_accumulate_reference(frames: torch.Tensor, vmin: float, vmax: float, 
         above.append((hot & m).to(torch.int64).sum(dim=0))
     return (torch.stack(nfr).to(torch.int64), torch.stack(cnt).to(torch.int32), torch.stack(s), torch.stack(sq),
             torch.stack(qmax).to(torch.int32), torch.stack(above).to(torch.int32))
+
+
+# K-12 per-pixel histograms: the defaults of the contract (docs/ARCHITECTURE.md, "Pixel histograms: the
+# integer contract").  The default window is 128 wide with 64 bins: bins of exactly 2.0, inv_w exactly 0.5.
+HIST_LO = -32.0
+HIST_HI = 96.0
+HIST_BINS = 64
+HIST_MAX_BINS = 1024
+HIST_MAX_FRAMES = 2 ** 31 - 1    # a bin gains at most 1 per frame: the int32 count is the only bound
+
+
+def validate_pixel_hist_params(lo, hi, nbins, n=None, frames_so_far=0, frames=0, what: str = "pixel_hist"):
+    """(lo, hi) as the float32 values the kernel sees, nbins as a Python int and the scale inv_w =
+    float32(float64(nbins) / (float64(hi) - float64(lo))) as a Python float -- or ValueError.  With ``n``
+    (elements per frame) also checks n * nbins < 2^31; with ``frames_so_far`` / ``frames`` that the run stays
+    at or below HIST_MAX_FRAMES = 2^31 - 1 frames."""
+    try:
+        nbins = operator.index(nbins)
+    except TypeError:
+        raise ValueError(f"{what}: nbins must be an integer, got {nbins!r}") from None
+    try:
+        with np.errstate(over="ignore"):   # a double beyond the float32 range becomes inf and is refused
+            flo, fhi = float(np.float32(lo)), float(np.float32(hi))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: the window must be two numbers") from None
+    if not (np.isfinite(flo) and np.isfinite(fhi)):
+        raise ValueError(f"{what}: the window must be finite, got [{lo}, {hi}]")
+    if not flo < fhi:
+        raise ValueError(f"{what}: the window needs lo < hi as float32, got [{lo}, {hi}]")
+    if not 1 <= nbins <= HIST_MAX_BINS:
+        raise ValueError(f"{what}: nbins must be in [1, {HIST_MAX_BINS}], got {nbins}")
+    with np.errstate(over="ignore", under="ignore"):
+        inv_w = float(np.float32(np.float64(nbins) / (np.float64(fhi) - np.float64(flo))))
+    if not np.isfinite(inv_w) or not inv_w > 0.0:
+        raise ValueError(f"{what}: the scale nbins / (hi - lo) = {inv_w} is not a finite positive float32")
+    if n is not None:
+        try:
+            n = operator.index(n)
+        except TypeError:
+            raise ValueError(f"{what}: the frame size must be an integer") from None
+        if n < 1 or n * nbins >= 2 ** 31:
+            raise ValueError(f"{what}: {n} elements x {nbins} bins: n >= 1 and n * nbins < 2^31 (int32 word indices)")
+    try:
+        frames_so_far, frames = operator.index(frames_so_far), operator.index(frames)
+    except TypeError:
+        raise ValueError(f"{what}: frame counts must be integers") from None
+    if frames_so_far < 0 or frames < 0 or frames_so_far + frames > HIST_MAX_FRAMES:
+        raise ValueError(f"{what}: {frames_so_far} + {frames} frames would take the run past {HIST_MAX_FRAMES} "
+                         "(the int32 count of a bin)")
+    return flo, fhi, nbins, inv_w
+
+
+def pixel_hist_reference(frames: torch.Tensor, lo: float, hi: float, nbins: int) -> torch.Tensor:
+    """K-12 golden: per-pixel histograms by exact INTEGER accumulation.  ``frames``: [F, ...] float32 (any
+    frame layout of n elements).  A sample v of pixel p contributes iff lo <= v <= hi as float32 (NaN fails,
+    +-inf is outside); it adds 1 to hist[p, b], b = min(nbins - 1, int(floor((v - lo) * inv_w))), where the
+    subtraction and the multiply are two float32 operations, each rounded to nearest, and inv_w =
+    float32(float64(nbins) / (float64(hi) - float64(lo))).  Returns hist int32 [n, nbins] of these frames
+    alone."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.float32:
+        raise ValueError(f"pixel_hist: frames must be a float32 tensor, got {getattr(frames, 'dtype', type(frames))}")
+    F = int(frames.shape[0]) if frames.dim() >= 1 else 0
+    if F < 1:
+        raise ValueError("pixel_hist: no frames")
+    x = frames.detach().cpu().reshape(F, -1)
+    n = int(x.shape[1])
+    flo, fhi, nbins, inv_w = validate_pixel_hist_params(lo, hi, nbins, n=n, frames=F)
+    hist = torch.zeros((n, nbins), dtype=torch.int64)
+    tlo, tinv = torch.tensor(flo, dtype=torch.float32), torch.tensor(inv_w, dtype=torch.float32)
+    for a in range(0, F, 64):   # bounded temporaries; integers add in any order
+        xb = x[a:a + 64]
+        ok = (xb >= flo) & (xb <= fhi)
+        d = xb - tlo                 # float32
+        y = d * tinv                 # float32, a second rounding
+        b = torch.floor(torch.where(ok, y, torch.zeros_like(y))).to(torch.int64).clamp_(0, nbins - 1)
+        hist.scatter_add_(1, b.t().contiguous(), ok.t().contiguous().to(torch.int64))
+    return hist.to(torch.int32)

@@ -16,7 +16,8 @@ consumer stream, releasing slots stream-ordered (BASELINE config 5); RadialProfi
 radial profile (K-08) the same way and keeps an exact integer run accumulator on the device;
 SparseFrameConsumer writes the pixels above a threshold as (index, value) pairs (K-10), optionally only
 of the frames the peak finder calls hits; PowderConsumer keeps the exact per-pixel run sums, spread and
-maximum of the calibrated frames (K-11), split into misses and hits by the same device-side filter.
+maximum of the calibrated frames (K-11), split into misses and hits by the same device-side filter;
+PixelHistConsumer keeps the exact per-pixel spectrum of the calibrated frames (K-12).
 """
 from __future__ import annotations
 
@@ -1282,3 +1283,97 @@ class PowderConsumer(_BatchConsumer):
         return PowderStats(self.detector, self.layout, self.shape, self.vmin, self.vmax, self.frac_bits,
                            self.thr_above, self.min_peaks, self._peak_dict(), h["frames"].copy(), h["cnt"].copy(),
                            h["sum"].copy(), h["sq"].copy(), h["above"].copy(), h["qmax"].copy())
+
+
+class PixelHistConsumer(_BatchConsumer):
+    """Consumer engine: batches of leased slots -> K-12 per-pixel histograms (csrc/pixhist.hip) ->
+    stream-ordered release.
+
+    Per run: how often every pixel read a value in each of ``nbins`` equal bins of ``[lo, hi]`` -- integers,
+    so the result is exact in any frame order.  The kernel owns a pixel per launch and uses no global
+    atomics, so every consumer stream has its OWN accumulator int32 ``[n, nbins]``; :meth:`synchronize` adds
+    them on the device and copies one result to the host."""
+
+    name = "hist"
+
+    def __init__(self, endpoint: QueueEndpoint, frame_shape, lo: Optional[float] = None, hi: Optional[float] = None,
+                 nbins: Optional[int] = None, detector: str = "", layout: str = "calib", batch: Optional[int] = None,
+                 stream_kind: str = CONSUMER_STREAM_KIND, streams: int = CONSUMER_STREAMS,
+                 ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
+        """frame_shape: the shape of a (calibrated) frame.  check_ring=False: the queue carries RAW
+        frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
+        from .ops import reference as _ref
+
+        self.shape = tuple(int(s) for s in frame_shape)
+        self.n = int(np.prod(self.shape))
+        self.lo, self.hi, self.nbins, self.inv_w = _ref.validate_pixel_hist_params(
+            _ref.HIST_LO if lo is None else lo, _ref.HIST_HI if hi is None else hi,
+            _ref.HIST_BINS if nbins is None else nbins, n=self.n, what="hist")
+        self.max_frames = _ref.HIST_MAX_FRAMES
+        self.detector, self.layout = str(detector), str(layout)
+        if check_ring:
+            if endpoint.ring.dtype != torch.float32:
+                raise ValueError(f"hist: the queue carries {endpoint.ring.dtype} frames, pixel histograms need "
+                                 "calibrated float32 ones")
+            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
+                raise ValueError(f"hist: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        self._host = np.zeros((self.n, self.nbins), np.int32)
+        self.acc_bytes = self.n * self.nbins * 4 * max(1, len(self.streams))
+        log.info("hist: %d accumulator(s) of %d x %d int32 = %.1f MB in all", max(1, len(self.streams)), self.n,
+                 self.nbins, self.acc_bytes / 1e6)
+        if self.gpu:
+            # one accumulator per stream; accumulator k is only ever touched by launches on stream k
+            self._acc = [torch.zeros((self.n, self.nbins), dtype=torch.int32, device=self.device)
+                         for _ in self.streams]
+
+    def _check_bound(self, n: int):
+        if self.frames + n > self.max_frames:
+            raise ValueError(f"hist: {self.frames} + {n} frames would take the run past {self.max_frames} "
+                             "(the int32 count of a bin)")
+
+    def _check_batch(self, n):
+        if n > self.batch:
+            raise ValueError(f"hist: {n} frames in a batch of at most {self.batch}")
+        self._check_bound(n)
+
+    def _limit(self, n_max):
+        self._check_bound(1)   # before any lease
+        return max(1, min(n_max, self.max_frames - self.frames))
+
+    def _launch_slots(self, C, slots, b, k, st):
+        C.pixel_hist_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.lo, self.hi, self.inv_w, self.nbins,
+                           int(self._acc[k].data_ptr()), int(st.cuda_stream))
+
+    def _launch_tensors(self, frames, b, k, st):
+        kernels.pixel_hist([t.reshape(-1) for t in frames], self.lo, self.hi, self.nbins, self._acc[k],
+                           frames_so_far=self.frames, stream=st)
+
+    def _reference(self, frames, meta):
+        from .ops import reference
+
+        x = torch.stack([t.reshape(-1) for t in frames])
+        self._host += reference.pixel_hist_reference(x, self.lo, self.hi, self.nbins).numpy()
+
+    def synchronize(self) -> np.ndarray:
+        """Wait for every batch, add the per-stream accumulators ON THE DEVICE (exact; a bin of the run is at
+        most its frames, which the bound keeps inside an int32) and copy the one result to the host.
+        Returns ``hist`` int32 [n, nbins]."""
+        if self.gpu:
+            self.sync_streams()
+            with torch.cuda.device(self.device):
+                total = self._acc[0]
+                if len(self._acc) > 1:
+                    total = self._acc[0].clone()
+                    for a in self._acc[1:]:
+                        total += a
+                self._host = total.cpu().numpy()
+                del total
+        return self._host
+
+    def stats(self):
+        """The (synchronised) run as a :class:`psana_ray_amd.hist.PixelHist`."""
+        from .hist import PixelHist
+
+        return PixelHist(self.detector, self.layout, self.shape, self.lo, self.hi, self.nbins, self.frames,
+                         self.synchronize().copy())

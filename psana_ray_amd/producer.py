@@ -77,13 +77,18 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--data_dir", type=str, default=None, help="raw-run files directory (or $PSANA_RAY_DATA)")
     g.add_argument("--chunk", type=int, default=64, help="frames per H2D copy / kernel launch (<= 64)")
     g.add_argument("--route", type=str, default="balanced", choices=["balanced", "local_first", "spread"])
-    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder"],
+    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder", "hist"],
                    help="also consume on every producer rank (co-located consumer, BASELINE config 5): the K-07 "
                         "peak finder, the K-08 radial profile (default binning of psana-ray-consumer), the K-09 "
                         "dark statistics (needs --mode raw; --out_dark writes the file), or the K-10 zero "
                         "suppression (--out_sparse writes the file; --sparse_thr ... --min_peaks as for "
                         "psana-ray-consumer --task sparse), or the K-11 powder statistics (--out_powder writes the "
-                        "file; --powder_vmin ... --min_peaks as for psana-ray-consumer --task powder)")
+                        "file; --powder_vmin ... --min_peaks as for psana-ray-consumer --task powder), or the K-12 "
+                        "per-pixel histograms (--out_hist writes the file; --hist_lo --hist_hi --hist_bins as for "
+                        "psana-ray-consumer --task hist)")
+    g.add_argument("--out_hist", type=str, default=None,
+                   help="--consumer_task hist: write the rank's per-pixel histograms (psana_ray_amd.hist.PixelHist "
+                        ".npz) here")
     g.add_argument("--out_powder", type=str, default=None,
                    help="--consumer_task powder: write the rank's powder statistics (psana_ray_amd.powder.PowderStats "
                         ".npz) here")
@@ -118,10 +123,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "the SDMA engines (utils/runtime_env.py)")
     g.add_argument("--local", action="store_true",
                    help="single-process queue: no rendezvous; requires --consumer_task (no external consumers)")
-    from .consumer import add_powder_arguments, add_sparse_arguments
+    from .consumer import add_hist_arguments, add_powder_arguments, add_sparse_arguments
 
     add_sparse_arguments(parser)
     add_powder_arguments(parser)
+    add_hist_arguments(parser)
     return parser
 
 
@@ -251,8 +257,8 @@ def main(argv=None) -> int:
     from .models import RadialBinning, make_geometry
     from .models.detector import Mode
     from .parallel.launch import bind_numa_to_device, detect, device_for
-    from .pipeline import (DarkStatsConsumer, PeakFinderConsumer, PowderConsumer, ProducerPipeline,
-                           RadialProfileConsumer, SparseFrameConsumer)
+    from .pipeline import (DarkStatsConsumer, PeakFinderConsumer, PixelHistConsumer, PowderConsumer,
+                           ProducerPipeline, RadialProfileConsumer, SparseFrameConsumer)
     from .queue.endpoint import EndOfStream, QueueEndpoint
     from .queue.ring import FrameRing, physical_slots
     from .queue.session import QueueSession
@@ -285,14 +291,15 @@ def main(argv=None) -> int:
                       "or a co-located --consumer_task")
             return 2
         mode = Mode.raw   # frames travel raw; DataReader applies read_mode
-    if args.consumer_task in ("radial", "sparse", "powder") and (mode == Mode.raw or int(args.panel_shards) > 1):
+    if args.consumer_task in ("radial", "sparse", "powder", "hist") and (mode == Mode.raw or int(args.panel_shards) > 1):
         log.error("--consumer_task %s needs whole calibrated frames (not --mode raw / --panel_shards)",
                   args.consumer_task)
         return 2
     if args.consumer_task == "dark" and (mode != Mode.raw or int(args.panel_shards) > 1):
         log.error("--consumer_task dark needs whole raw frames (--mode raw, no --panel_shards)")
         return 2
-    for flag, task in (("out_sparse", "sparse"), ("out_dark", "dark"), ("out_powder", "powder")):
+    for flag, task in (("out_sparse", "sparse"), ("out_dark", "dark"), ("out_powder", "powder"),
+                       ("out_hist", "hist")):
         if getattr(args, flag) is not None and args.consumer_task != task:
             log.error("--%s belongs to --consumer_task %s", flag, task)
             return 2
@@ -417,7 +424,7 @@ def main(argv=None) -> int:
             # consumer thread, at the end of the stream), report(result or None, frames consumed) after the join
             each = None
 
-            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder merge)
+            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder / .hist merge)
                 root, ext = os.path.splitext(path)
                 return path if size == 1 else f"{root}.r{rank}{ext}"
 
@@ -488,6 +495,22 @@ def main(argv=None) -> int:
                         path = rank_path(args.out_powder)
                         ps.save(path)
                         log.info("Rank %d: powder statistics written to %s", rank, path)
+            elif args.consumer_task == "hist":
+                try:
+                    cons = PixelHistConsumer(ep, frame_shape, lo=args.hist_lo, hi=args.hist_hi, nbins=args.hist_bins,
+                                             detector=args.detector_name, layout=mode.value)
+                except ValueError as e:
+                    log.error("--consumer_task hist: %s", e)
+                    return 2
+                finish = cons.stats
+
+                def report(ph, consumed):
+                    print(f"Consumer {rank} hist: frames={0 if ph is None else ph.frames} "
+                          f"samples={0 if ph is None else int(ph.hist.sum(dtype='int64'))}", flush=True)
+                    if ph is not None and args.out_hist:
+                        path = rank_path(args.out_hist)
+                        ph.save(path)
+                        log.info("Rank %d: pixel histograms written to %s", rank, path)
             else:
                 cons = PeakFinderConsumer(ep, frame_shape, PeakFinderParams())
                 finish = cons.synchronize
