@@ -413,6 +413,82 @@ def main(argv=None):
                     "chunks16_touched_bytes": touched[k][1], "bytes_vs_read_floor": round(nbytes / fbytes, 3),
                     "vs_read_floor": round(mh[0] / mr[0], 3), "vs_powder": round(mh[0] / mp[0], 3),
                     "TB_per_s": round(nbytes / mh[0] / 1e12, 3)}, frames=FR)
+    if want("photons"):
+        # K-13 photon counting: 64 SEPARATELY allocated float32 frames per launch, with the read floor and the
+        # powder kernel (one class) on the SAME frames in the same process -- alternating rounds, the median
+        # round of each.  Inputs are synthetic: "background" is Poisson(0.02) photons per pixel of 10.0 each plus
+        # Gaussian noise of 0.1 photon (pixels with k >= 1 are rare: the LDS counters and the merge atomics are
+        # nearly idle), "dense" gives EVERY pixel 1 .. 3 photons (every lane of every wave counts into the same
+        # few LDS words: the worst case of the counters).  Bytes: 4 B per pixel and frame, a read and a write of
+        # the 16 B of accumulators per pixel and launch, and 1 B per pixel and frame where kmap is written.
+        from psana_ray_amd.ops.reference import (POWDER_FRAC_BITS, POWDER_QMAX_NONE, POWDER_THR_ABOVE, POWDER_VMAX,
+                                                 POWDER_VMIN)
+
+        FR, rounds, adu = 64, 5, 10.0
+        C = _ext.load()
+        gen = torch.Generator(device=dev).manual_seed(13)
+        shape3 = spec.frame_shape if len(spec.frame_shape) == 3 else (1, *spec.frame_shape)
+        rate = torch.full((npix,), 0.02, device=dev)
+        inputs = {"background": [(torch.poisson(rate, generator=gen) + 0.1 * torch.randn(npix, generator=gen, device=dev))
+                                 * adu for _ in range(FR)],
+                  "dense": [(1.0 + torch.randint(0, 3, (npix,), generator=gen, device=dev).float()
+                             + 0.3 * torch.rand(npix, generator=gen, device=dev)) * adu for _ in range(FR)]}
+        # (name, input, kmap, launch variant): the shape in use first, then the background case in the other launch
+        # shapes that were tried: 2 frames in flight instead of 4, and one block per workgroup (no grid cap)
+        cases = [("background", "background", False, 0), ("dense", "dense", False, 0),
+                 ("background + kmap", "background", True, 0), ("background, 2 frames in flight", "background", False, 1),
+                 ("background, grid cap 4096", "background", False, 4096 << 8),
+                 ("background, grid cap 512", "background", False, 512 << 8)]
+        acc = (torch.zeros(npix, dtype=torch.int32, device=dev), torch.zeros(npix, dtype=torch.int64, device=dev),
+               torch.zeros(npix, dtype=torch.int32, device=dev))
+        pk = torch.zeros((FR, 1, 8), dtype=torch.int32, device=dev)
+        tot = torch.zeros((FR, 1), dtype=torch.int64, device=dev)
+        kmap = torch.zeros((FR, npix), dtype=torch.uint8, device=dev)
+        kbar = {}
+        for name, frames in inputs.items():
+            kernels.photons(frames, shape3, adu, *acc, pk, tot)
+            torch.cuda.synchronize()
+            kbar[name] = float(tot.sum()) / (FR * npix)
+        fp64 = [int(t.data_ptr()) for t in inputs["background"]]
+        sums = torch.zeros(FR, dtype=torch.float32, device=dev)
+        pacc = (torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros((1, npix), dtype=torch.int32, device=dev),
+                torch.zeros((1, npix), dtype=torch.int64, device=dev), torch.zeros((1, npix), dtype=torch.int64, device=dev),
+                torch.full((1, npix), POWDER_QMAX_NONE, dtype=torch.int32, device=dev),
+                torch.zeros((1, npix), dtype=torch.int32, device=dev))
+
+        def phot_fn(k):
+            _, inp, with_map, variant = cases[k]
+            return lambda: kernels.photons(inputs[inp], shape3, adu, *acc, pk, tot, kmap=kmap if with_map else None,
+                                           _variant=variant)
+
+        t_read, t_pw, t_ph = [], [], {k: [] for k in range(len(cases))}
+        for _ in range(rounds):
+            t_read.append(timeit(lambda: C.read_f32(fp64, npix, 16, False, int(sums.data_ptr()), _ext.stream_handle()),
+                                 a.iters))
+            for t, v in zip(pacc, (0, 0, 0, 0, POWDER_QMAX_NONE, 0)):   # every timed window starts a run
+                t.fill_(v)
+            t_pw.append(timeit(lambda: kernels.powder_accumulate(inputs["background"], POWDER_VMIN, POWDER_VMAX,
+                                                                 POWDER_FRAC_BITS, POWDER_THR_ABOVE, *pacc), a.iters))
+            for k in t_ph:
+                for t in acc:
+                    t.zero_()
+                t_ph[k].append(timeit(phot_fn(k), a.iters))
+        med = lambda ts: sorted(ts)[rounds // 2]   # noqa: E731
+        us = lambda ts: [round(t[0] * 1e6 / FR, 3) for t in ts]   # noqa: E731
+        mr, mp = med(t_read), med(t_pw)
+        fbytes = FR * npix * 4
+        report("read_f32 reference (K=16)", mr, fbytes, {"rounds_us_per_frame": us(t_read)}, frames=FR)
+        report("powder(NC=1)", mp, fbytes + npix * 56, {"rounds_us_per_frame": us(t_pw),
+                                                        "vs_read_floor": round(mp[0] / mr[0], 3)}, frames=FR)
+        for k, ts in t_ph.items():
+            name, inp, with_map, variant = cases[k]
+            mh = med(ts)
+            nbytes = fbytes + npix * 32 + (FR * npix if with_map else 0)
+            report(f"photons({name})", mh, nbytes,
+                   {"photons_per_pixel": round(kbar[inp], 4), "kmap": with_map, "variant": variant,
+                    "rounds_us_per_frame": us(ts),
+                    "bytes_vs_read_floor": round(nbytes / fbytes, 3), "vs_read_floor": round(mh[0] / mr[0], 3),
+                    "vs_powder": round(mh[0] / mp[0], 3), "TB_per_s": round(nbytes / mh[0] / 1e12, 3)}, frames=FR)
     if want("h2d"):
         C = _ext.load()
         hp = src.pool

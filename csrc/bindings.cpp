@@ -99,7 +99,7 @@ static FramePtrs make_ptrs(const std::vector<uint64_t>& in, const std::vector<ui
 }
 
 // The consumers' ring-slot bindings (peakfind_slots, radial_slots, dark_slots, sparsify_slots,
-// powder_slots, pixel_hist_slots): the two
+// powder_slots, pixel_hist_slots, photons_slots): the two
 // checks they share, then fn(index of the chunk's first slot, its slot pointers) for every chunk of at
 // most kMaxFrames slots.
 template <class Fn>
@@ -457,6 +457,40 @@ PYBIND11_MODULE(_C, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("pixel_hist_tile_pixels", &pr::pixel_hist_tile_pixels, py::arg("nbins"),
         "consecutive pixels one workgroup of the K-12 kernel owns at this nbins");
+
+  m.def("photons",
+        [](const std::vector<uint64_t>& in, int P, int H, int W, float inv, float vmax, float thr_seed, float thr_total,
+           uint64_t mask, uint64_t roi, int n_roi, uint64_t kmap, uint64_t cnt, uint64_t psum, uint64_t occ, uint64_t pk,
+           uint64_t tot, uint64_t stream, int variant) {
+          pr::launch_photons(make_ptrs(in, in), (int)in.size(), P, H, W, inv, vmax, thr_seed, thr_total, mask, roi, n_roi,
+                             kmap, cnt, psum, occ, pk, tot, stream, variant);
+        },
+        py::arg("in_ptrs"), py::arg("P"), py::arg("H"), py::arg("W"), py::arg("inv"), py::arg("vmax"),
+        py::arg("thr_seed"), py::arg("thr_total"), py::arg("mask"), py::arg("roi"), py::arg("n_roi"), py::arg("kmap"),
+        py::arg("cnt"), py::arg("psum"), py::arg("occ"), py::arg("pk"), py::arg("tot"), py::arg("stream"),
+        py::arg("variant") = 0,
+        "K-13 photon counting of up to 64 float32 frames [P, H, W]: adds cnt / psum / occ [n], fills pk / tot (/ kmap)");
+  // consumer hot path: ring slots -> photon accumulators + per-frame P(k) rows, one native call
+  m.def("photons_slots",
+        [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int P, int H, int W, float inv,
+           float vmax, float thr_seed, float thr_total, uint64_t mask, uint64_t roi, int n_roi, uint64_t cnt,
+           uint64_t psum, uint64_t occ, uint64_t pk, uint64_t tot, uint64_t stream) {
+          for_slot_chunks(pool, slot_bytes, slots, (int64_t)P * H * W * 4, "photons_slots",
+                          [&](int a, const std::vector<uint64_t>& in) {
+                            const uint64_t row = (uint64_t)a * n_roi;
+                            pr::launch_photons(make_ptrs(in, in), (int)in.size(), P, H, W, inv, vmax, thr_seed, thr_total,
+                                               mask, roi, n_roi, 0, cnt, psum, occ, pk + row * 32, tot + row * 8, stream);
+                          });
+        },
+        py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("P"), py::arg("H"), py::arg("W"),
+        py::arg("inv"), py::arg("vmax"), py::arg("thr_seed"), py::arg("thr_total"), py::arg("mask"), py::arg("roi"),
+        py::arg("n_roi"), py::arg("cnt"), py::arg("psum"), py::arg("occ"), py::arg("pk"), py::arg("tot"),
+        py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("photons_lane_pixels", &pr::photons_lane_pixels, py::arg("W"),
+        "pixels one lane of the K-13 kernel owns at this panel width (4, or 1 when W % 4 != 0)");
+  m.def("photons_block_pixels", &pr::photons_block_pixels, py::arg("W"),
+        "consecutive pixels one block of lanes of the K-13 kernel owns at this panel width");
+  m.def("photons_max_grid", &pr::photons_max_grid, "workgroups of the K-13 kernel at most");
 
   m.def("copy_h2d_kernel",
         [](uint64_t dst, uint64_t src, int64_t bytes, int workgroups, uint64_t stream) {

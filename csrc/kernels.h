@@ -106,4 +106,20 @@ int pixel_hist_tile_pixels(int nbins);
 void launch_pixel_hist(const FramePtrs& fp, int nframes, int64_t n, float lo, float hi, float inv_w, int nbins,
                        uint64_t hist, uint64_t stream,
                        int layout = 0);   // measurements only: 1 = word-major LDS tile, 2 = unpadded row pitch
+// K-13 photon counting (csrc/photons.hip): up to kMaxFrames float32 frames of shape [P, H, W] -> photons per
+// pixel k (whole photons by floor of v * inv, plus one where a seed's remainder and its largest 4-connected
+// neighbour remainder of the same panel reach thr_total).  ADDS to the planar run accumulators cnt int32 /
+// psum int64 / occ int32 [n] (never clears; one owner lane per pixel, so two launches in flight must not
+// share a set); clears on the stream, then fills pk int32 [F, n_roi, 8] and tot int64 [F, n_roi]; writes
+// kmap uint8 [F, n] when kmap != 0.  mask uint8 [n] (0 = all kept), roi uint8 [n] labels (0 = one ROI).
+// inv = float32(1 / adu_per_photon) from the caller.  photons_block_pixels: the consecutive pixels one block
+// of lanes owns (a lane owns photons_lane_pixels: 4 when W % 4 == 0, else 1); a workgroup owns several blocks
+// once there are more than photons_max_grid of them.
+int photons_lane_pixels(int W);
+int photons_block_pixels(int W);
+int photons_max_grid();
+void launch_photons(const FramePtrs& fp, int nframes, int P, int H, int W, float inv, float vmax, float thr_seed,
+                    float thr_total, uint64_t mask, uint64_t roi, int n_roi, uint64_t kmap, uint64_t cnt,
+                    uint64_t psum, uint64_t occ, uint64_t pk, uint64_t tot, uint64_t stream,
+                    int variant = 0);   // measurements only: bit 0 = 2 frames in flight, bits 8.. = grid cap
 }  // namespace pr

@@ -14,11 +14,12 @@ suppression: the pixels inside a value window as (index, value) pairs, optionall
 at least ``--min_peaks`` peaks), ``powder`` (on-GPU K-11 powder statistics: exact per-pixel run sum,
 spread, maximum and count above a threshold of the calibrated frames, misses and hits apart with
 ``--min_peaks``), ``hist`` (on-GPU K-12 per-pixel histograms: the exact spectrum of every pixel of the
-calibrated frames, for gain maps) or ``none``.  ``--out`` writes the peak lists / the radial accumulator / the dark
+calibrated frames, for gain maps), ``photons`` (on-GPU K-13 photon counting: photons per pixel with psana's
+neighbour merge, run maps and the per-frame P(k) of up to 8 ROIs) or ``none``.  ``--out`` writes the peak lists / the radial accumulator / the dark
 statistics / the sparse frames / the powder statistics to an ``.npz`` (several consumers' radial files add
 with ``psana_ray_amd.radial.merge``, dark files with ``psana_ray_amd.dark.merge``, sparse files join with
 ``psana_ray_amd.sparse.merge``, powder files merge with ``psana_ray_amd.powder.merge``, histogram files with
-``psana_ray_amd.hist.merge``).
+``psana_ray_amd.hist.merge``, photon files with ``psana_ray_amd.photons.merge``).
 """
 from __future__ import annotations
 
@@ -43,13 +44,14 @@ def build_parser():
     ap.add_argument("--ray_namespace", type=str, default=DEFAULT_RAY_NAMESPACE)
     ap.add_argument("--queue_name", type=str, default=DEFAULT_QUEUE_NAME)
     ap.add_argument("--device", type=str, default=None)
-    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "hist", "train", "none"],
+    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "train", "none"],
                     help="train: online PeakNetLite training from peak-finder labels (trainer.py); radial: radial "
                          "profile I(r) / I(q) of every frame + run accumulator (--nbins ... --radial_mask); dark: "
                          "per-pixel dark-run statistics of a RAW queue (--adu_min / --adu_max); sparse: zero-suppressed "
                          "frames to disk (--sparse_thr ... --min_peaks); powder: per-pixel run sums / spread / max of the "
                          "calibrated frames, misses and hits apart (--powder_vmin ... --min_peaks); hist: per-pixel "
-                         "histograms of the calibrated frames (--hist_lo --hist_hi --hist_bins)")
+                         "histograms of the calibrated frames (--hist_lo --hist_hi --hist_bins); photons: photons per pixel "
+                         "of the calibrated frames (--adu_per_photon ... --photon_roi)")
     ap.add_argument("--lr", type=float, default=1e-3, help="--task train: AdamW learning rate")
     ap.add_argument("--save", type=str, default=None, help="--task train: write the model state_dict here")
     ap.add_argument("--ddp", action="store_true",
@@ -69,7 +71,8 @@ def build_parser():
                          "when --task radial; the dark statistics (psana_ray_amd.dark.DarkStats npz) when --task dark; "
                          "the sparse frames (psana_ray_amd.sparse.SparseFrames npz) when --task sparse; the powder "
                          "statistics (psana_ray_amd.powder.PowderStats npz) when --task powder; the per-pixel histograms "
-                         "(psana_ray_amd.hist.PixelHist npz) when --task hist")
+                         "(psana_ray_amd.hist.PixelHist npz) when --task hist; the photon statistics "
+                         "(psana_ray_amd.photons.PhotonStats npz) when --task photons")
     g = ap.add_argument_group("--task radial")
     g.add_argument("--nbins", type=int, default=512, help="radial bins (1 .. 4096)")
     g.add_argument("--center", type=str, default=None, help="beam centre Y,X in image pixels (default: image centre)")
@@ -90,6 +93,7 @@ def build_parser():
     add_sparse_arguments(ap)
     add_powder_arguments(ap)
     add_hist_arguments(ap)
+    add_photon_arguments(ap)
     ap.add_argument("--timeout", type=float, default=300.0)
     ap.add_argument("--metrics_interval", type=float, default=10.0, help="seconds between rate lines; 0 disables")
     ap.add_argument("--metrics_json", type=str, default=None, help="append per-interval metrics as JSON lines")
@@ -138,6 +142,50 @@ def add_hist_arguments(ap):
     g.add_argument("--hist_bins", type=int, default=64,
                    help="equal bins of [hist_lo, hist_hi], 1 .. 1024 (default 64: bins of 2.0); pixels x bins must "
                         "stay below 2^31, and every consumer stream holds pixels x bins x 4 bytes on the device")
+
+
+def add_photon_arguments(ap):
+    """The flags of ``--task photons`` (the producer CLI's ``--consumer_task photons`` takes the same)."""
+    g = ap.add_argument_group("--task photons")
+    g.add_argument("--adu_per_photon", type=float, default=None,
+                   help="calibrated value of one photon (required for the task)")
+    g.add_argument("--photon_vmax", type=float, default=None,
+                   help="samples above are ignored (default 250 x adu_per_photon; floor(vmax / adu_per_photon) "
+                        "must stay at or below 254)")
+    g.add_argument("--photon_seed", type=float, default=0.5,
+                   help="a pixel's fractional remainder must reach this to seed a merge (default 0.5)")
+    g.add_argument("--photon_total", type=float, default=0.9,
+                   help="a seed's remainder plus its largest neighbour's must reach this to count one more photon "
+                        "(default 0.9)")
+    g.add_argument("--photon_mask", type=str, default=None,
+                   help=".npy keep-mask of the frames' shape: non-zero = keep (default: every pixel)")
+    g.add_argument("--photon_roi", type=str, default=None,
+                   help=".npy uint8 ROI labels of the frames' shape: 0 .. 7, 255 = in no ROI (default: one ROI of "
+                        "every pixel); P(k) and the photon total are kept per frame and ROI")
+
+
+def load_photon_maps(args, shape):
+    """(mask, roi) of ``--photon_mask`` / ``--photon_roi`` as uint8 [n] arrays or None; ValueError for another
+    shape or non-integer labels (an image may come without its leading axis of 1)."""
+    import numpy as np
+
+    shape = tuple(shape)
+    out = []
+    for flag, path in (("--photon_mask", args.photon_mask), ("--photon_roi", args.photon_roi)):
+        if not path:
+            out.append(None)
+            continue
+        a = np.load(path)   # allow_pickle stays False
+        if tuple(a.shape) != shape and not (shape[0] == 1 and tuple(a.shape) == shape[1:]):
+            raise ValueError(f"{flag} is {tuple(a.shape)}, the frames are {shape}")
+        if flag == "--photon_mask":
+            a = (a != 0).astype(np.uint8)
+        elif a.dtype != np.uint8:
+            if a.dtype.kind not in "iu" or a.size and (int(a.min()) < 0 or int(a.max()) > 255):
+                raise ValueError(f"{flag} must hold integer labels 0 .. 7 or 255, got {a.dtype}")
+            a = a.astype(np.uint8)
+        out.append(np.ascontiguousarray(a).reshape(-1))
+    return tuple(out)
 
 
 def _init_data_parallel(device) -> int:
@@ -547,8 +595,52 @@ def run_hist(args, reader, stop, progress) -> int:
     return rc
 
 
+def run_photons(args, reader, stop, progress) -> int:
+    """--task photons: count until the end of the stream; ``progress["n"]`` counts frames."""
+    from .pipeline import PhotonConsumer
+
+    cid = reader.consumer_id
+    if not _has_whole_frames(reader, "photons", "photon counting"):
+        return 2
+    cal = reader.calibrator
+    try:
+        name, layout, shape = sparse_layout(reader, args, needs="photon counting needs")
+    except ValueError as e:
+        log.error("--task photons: %s", e)
+        return 2
+    if not name:
+        log.error("--task photons: the session does not name its detector; pass --detector_name")
+        return 2
+    try:
+        mask, roi = load_photon_maps(args, shape)
+        cons = PhotonConsumer(reader.endpoint, shape, args.adu_per_photon, vmax=args.photon_vmax,
+                              thr_seed=args.photon_seed, thr_total=args.photon_total, mask=mask, roi=roi,
+                              detector=name, layout=layout, batch=args.batch, check_ring=cal is None)
+    except (ValueError, KeyError, OSError) as e:
+        log.error("--task photons: %s", e)
+        return 2
+    pp = cons.params
+    print(f"Consumer {cid} photons: adu_per_photon={pp.adu_per_photon:g} vmax={pp.vmax:g} seed={pp.thr_seed:g} "
+          f"total={pp.thr_total:g} rois={cons.n_roi}", flush=True)
+    try:
+        rc = _drive(args, reader, stop, progress, cons,
+                    raw_meta=None if cal is None else lambda it: (it.rank, it.idx, it.gevt, it.photon_energy))
+    except ValueError as e:   # the run reached 2^31 - 1 frames
+        log.error("--task photons: %s", e)
+        rc = 2
+    st = cons.stats()
+    print(f"Consumer {cid} photons: frames={st.frames} detector={name} layout={layout} "
+          f"samples={int(st.cnt.sum(dtype='int64'))} photons={int(st.psum.sum())}", flush=True)
+    if args.out:
+        st.save(args.out)
+    return rc
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
+    if args.task == "photons" and args.adu_per_photon is None:
+        print("psana-ray-consumer: --task photons needs --adu_per_photon", file=sys.stderr)
+        return 2
     logging.basicConfig(level=getattr(logging, args.log_level), format="%(asctime)s - %(levelname)s - %(message)s")
     import numpy as np
     import torch
@@ -584,7 +676,7 @@ def main(argv=None) -> int:
                             json_path=args.metrics_json).start()
         pf = None
         run_task = {"radial": run_radial, "dark": run_dark, "sparse": run_sparse, "powder": run_powder,
-                    "hist": run_hist}.get(args.task)
+                    "hist": run_hist, "photons": run_photons}.get(args.task)
         if run_task is not None:   # the tasks that run a pipeline consumer to the end of the stream
             progress = {"n": 0}
             registry.register(args.task, lambda: {"frames_consumed": progress["n"]})

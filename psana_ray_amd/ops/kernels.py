@@ -1,4 +1,4 @@
-"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-12).
+"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-13).
 
 Every wrapper checks device / dtype / shape / contiguity / alignment on the host BEFORE the
 launch (a mis-shaped launch of a hand-written kernel can fault the GPU), splits batches into
@@ -395,6 +395,99 @@ def pixel_hist(frames: Sequence[torch.Tensor], lo: float, hi: float, nbins: int,
     s = _ext.stream_handle(stream)
     for a, b in _chunks(F):
         C.pixel_hist([_ptr(t) for t in frames[a:b]], n, flo, fhi, inv_w, nbins, _ptr(hist), s, _layout)
+
+
+def photons_lane_pixels(W: int) -> int:
+    """The consecutive pixels one lane of the K-13 kernel owns at panel width ``W``: 4, or 1 when W % 4 != 0
+    (the scalar path)."""
+    return int(_ext.load().photons_lane_pixels(int(W)))
+
+
+def photons_block_pixels(W: int) -> int:
+    """The consecutive pixels one block of lanes of the K-13 kernel owns at panel width ``W``; frames of more
+    than ``photons_max_grid()`` blocks give a workgroup several.  The sizes around both are where the kernel
+    changes path."""
+    return int(_ext.load().photons_block_pixels(int(W)))
+
+
+def photons_max_grid() -> int:
+    """Workgroups of the K-13 kernel at most."""
+    return int(_ext.load().photons_max_grid())
+
+
+def _photon_map(t, n: int, dev, name: str, what: str, R: Optional[int] = None):
+    """A keep-mask / ROI label map on the device: uint8 [n], contiguous, 16-B aligned.  Labels are validated
+    against ``R`` once per tensor (the check reads the map back; the result is cached on the tensor)."""
+    if t is None:
+        return 0
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.numel() != n or t.device != dev \
+            or not t.is_contiguous() or t.data_ptr() % 16:
+        raise ValueError(f"{what}: {name} must be a contiguous, 16-B aligned uint8 tensor of {n} elements on {dev}")
+    if R is not None and getattr(t, "_pr_checked_roi", None) != (n, R):
+        if bool(((t >= R) & (t != 255)).any()):
+            raise ValueError(f"{what}: a label >= n_roi = {R} other than 255")
+        t._pr_checked_roi = (n, R)
+    return _ptr(t)
+
+
+def photons(frames: Sequence[torch.Tensor], shape, adu_per_photon, cnt: torch.Tensor, psum: torch.Tensor,
+            occ: torch.Tensor, pk: torch.Tensor, tot: torch.Tensor, vmax=None, thr_seed=None, thr_total=None,
+            mask: Optional[torch.Tensor] = None, roi: Optional[torch.Tensor] = None, n_roi: Optional[int] = None,
+            kmap: Optional[torch.Tensor] = None, frames_so_far: int = 0, stream=None, _variant: int = 0):
+    """K-13 photon counting (csrc/photons.hip; contract: ops.reference.photon_count_reference).
+    frames: F float32 tensors of ``shape`` = [P, H, W] (or [H, W]) on one GPU.  ADDS per pixel the samples
+    (``cnt`` int32 [n]), the photons (``psum`` int64 [n]) and the frames with a photon (``occ`` int32 [n]) to
+    accumulators the caller zeroes once per run and whose frames so far it passes in ``frames_so_far`` (a run
+    holds 2^31 - 1 frames); fills ``pk`` int32 [F, R, 8] and ``tot`` int64 [F, R] (cleared by the call) and,
+    when given, ``kmap`` uint8 [F, n].  ``mask`` / ``roi``: uint8 [n] on the device; ``n_roi`` = R (default 1;
+    labels 0 .. R - 1, 255 = none).  One lane owns a pixel: launches in flight on DIFFERENT streams must not
+    share an accumulator set.  Everything is checked here, before any launch.  ``_variant`` selects a launch
+    shape for measurements (bit 0: 2 frames in flight instead of 4; bits 8 and up: another grid cap)."""
+    from .reference import PHOTON_MAX_ROI, PHOTON_PK_BINS, photon_shape, validate_photon_params
+
+    what = "photons"
+    F = len(frames)
+    pp = validate_photon_params(adu_per_photon, vmax, thr_seed, thr_total, frames_so_far=frames_so_far, frames=F,
+                                what=what)
+    P, H, W = photon_shape(shape, what)
+    n = P * H * W
+    try:
+        R = 1 if n_roi is None else operator.index(n_roi)
+    except TypeError:
+        raise ValueError(f"{what}: n_roi must be an integer, got {n_roi!r}") from None
+    if not 1 <= R <= PHOTON_MAX_ROI:
+        raise ValueError(f"{what}: {R} ROIs; 1 .. {PHOTON_MAX_ROI} are possible")
+    if roi is None and R != 1:
+        raise ValueError(f"{what}: {R} ROIs need labels")
+    if F == 0:
+        return
+    if not isinstance(frames[0], torch.Tensor):
+        raise ValueError(f"{what}: frames must be tensors")
+    dev = frames[0].device
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: frames on {dev}, expected a GPU")
+    _check_frames(frames, torch.float32, n, dev, f"{what} in")
+    for t, dt, name in ((cnt, torch.int32, "cnt"), (psum, torch.int64, "psum"), (occ, torch.int32, "occ")):
+        if not isinstance(t, torch.Tensor) or t.shape != (n,) or t.dtype != dt or t.device != dev \
+                or not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError(f"{what}: {name} must be a contiguous, 16-B aligned {dt} [{n}] tensor on {dev}")
+    for t, dt, shp, name in ((pk, torch.int32, (F, R, PHOTON_PK_BINS), "pk"), (tot, torch.int64, (F, R), "tot")):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shp or t.dtype != dt or t.device != dev \
+                or not t.is_contiguous() or t.data_ptr() % 8:
+            raise ValueError(f"{what}: {name} must be a contiguous {dt} {list(shp)} tensor on {dev}")
+    if kmap is not None and (not isinstance(kmap, torch.Tensor) or tuple(kmap.shape) != (F, n)
+                             or kmap.dtype != torch.uint8 or kmap.device != dev or not kmap.is_contiguous()
+                             or (W % 4 == 0 and kmap.data_ptr() % 4)):   # the quad path stores words
+        raise ValueError(f"{what}: kmap must be a contiguous, 4-B aligned uint8 [{F}, {n}] tensor on {dev}")
+    pm = _photon_map(mask, n, dev, "mask", what)
+    pr = _photon_map(roi, n, dev, "roi", what, R)
+    C = _ext.load()
+    s = _ext.stream_handle(stream)
+    for a, b in _chunks(F):
+        # chunks start at multiples of 64 frames: kmap[a] stays 4-B aligned when W % 4 == 0
+        C.photons([_ptr(t) for t in frames[a:b]], P, H, W, pp.inv, pp.vmax, pp.thr_seed, pp.thr_total, pm, pr, R,
+                  0 if kmap is None else _ptr(kmap[a:b]), _ptr(cnt), _ptr(psum), _ptr(occ), _ptr(pk[a:b]),
+                  _ptr(tot[a:b]), s, int(_variant))
 
 
 # elements per chunk of the K-10 scan (csrc/kernels.h kSparseChunk): one directory entry per chunk

@@ -9,7 +9,7 @@ caught too.
 from __future__ import annotations
 
 import operator
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -528,3 +528,184 @@ def pixel_hist_reference(frames: torch.Tensor, lo: float, hi: float, nbins: int)
         b = torch.floor(torch.where(ok, y, torch.zeros_like(y))).to(torch.int64).clamp_(0, nbins - 1)
         hist.scatter_add_(1, b.t().contiguous(), ok.t().contiguous().to(torch.int64))
     return hist.to(torch.int32)
+
+
+# K-13 photon counting: the defaults and bounds of the contract (docs/ARCHITECTURE.md, "Photon counting: the
+# integer contract").
+PHOTON_THR_SEED = 0.5
+PHOTON_THR_TOTAL = 0.9
+PHOTON_MAX_WHOLE = 254           # floor(vmax * inv) at most: a merge on top still fits the byte of kmap
+PHOTON_VMAX_PHOTONS = 250        # the default vmax is this many adu_per_photon
+PHOTON_MAX_ROI = 8
+PHOTON_ROI_NONE = 255            # the label of a pixel in no ROI
+PHOTON_PK_BINS = 8               # pk[..., j] counts k == j + 1, the last bin k >= 8
+PHOTON_MAX_FRAMES = 2 ** 31 - 1  # cnt and occ gain at most 1 per frame (psum at most 255: far inside an int64)
+
+
+class PhotonParams(NamedTuple):
+    """The validated parameters of K-13 as the kernel sees them (every float a float32 value)."""
+    adu_per_photon: float
+    inv: float          # float32(1 / float64(adu_per_photon))
+    vmax: float
+    thr_seed: float
+    thr_total: float
+
+
+class PhotonCounts(NamedTuple):
+    """What :func:`photon_count_reference` returns (the accumulators are the increments of these frames)."""
+    kmap: torch.Tensor   # uint8 [F, n]
+    cnt: torch.Tensor    # int32 [n]
+    psum: torch.Tensor   # int64 [n]
+    occ: torch.Tensor    # int32 [n]
+    pk: torch.Tensor     # int32 [F, R, 8]
+    tot: torch.Tensor    # int64 [F, R]
+
+
+def validate_photon_params(adu_per_photon, vmax=None, thr_seed=None, thr_total=None, frames_so_far=0, frames=0,
+                           what: str = "photons") -> PhotonParams:
+    """The parameters as float32 values and the scale ``inv = float32(1.0 / float64(adu_per_photon))`` -- or
+    ValueError.  ``vmax`` None: ``PHOTON_VMAX_PHOTONS * adu_per_photon``.  Requires adu_per_photon > 0 with a
+    finite positive inv, ``floor(float32(vmax) * inv) <= 254`` and ``0 < thr_seed <= thr_total < 2``; with
+    ``frames_so_far`` / ``frames`` that the run stays at or below PHOTON_MAX_FRAMES = 2^31 - 1 frames."""
+    if isinstance(adu_per_photon, PhotonParams):
+        adu_per_photon, _inv, vmax, thr_seed, thr_total = adu_per_photon
+    try:
+        with np.errstate(over="ignore", under="ignore"):
+            adu = float(np.float32(adu_per_photon))
+            fmax = float(np.float32(PHOTON_VMAX_PHOTONS * adu if vmax is None else vmax))
+            ts = float(np.float32(PHOTON_THR_SEED if thr_seed is None else thr_seed))
+            tt = float(np.float32(PHOTON_THR_TOTAL if thr_total is None else thr_total))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: adu_per_photon, vmax and the thresholds must be numbers") from None
+    if not (np.isfinite(adu) and adu > 0.0):
+        raise ValueError(f"{what}: adu_per_photon must be finite and positive, got {adu_per_photon}")
+    with np.errstate(over="ignore", under="ignore", divide="ignore"):
+        inv = float(np.float32(1.0 / np.float64(adu)))
+    if not (np.isfinite(inv) and inv > 0.0):
+        raise ValueError(f"{what}: the scale 1 / adu_per_photon = {inv} is not a finite positive float32")
+    if fmax != fmax:
+        raise ValueError(f"{what}: vmax is NaN")
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        whole = np.floor(np.float32(fmax) * np.float32(inv))
+    if not whole <= PHOTON_MAX_WHOLE:
+        raise ValueError(f"{what}: floor(vmax / adu_per_photon) = {whole} must be at most {PHOTON_MAX_WHOLE} "
+                         "(photons per pixel fit a byte)")
+    if not 0.0 < ts <= tt < 2.0:
+        raise ValueError(f"{what}: the thresholds need 0 < thr_seed <= thr_total < 2, got {thr_seed}, {thr_total}")
+    try:
+        frames_so_far, frames = operator.index(frames_so_far), operator.index(frames)
+    except TypeError:
+        raise ValueError(f"{what}: frame counts must be integers") from None
+    if frames_so_far < 0 or frames < 0 or frames_so_far + frames > PHOTON_MAX_FRAMES:
+        raise ValueError(f"{what}: {frames_so_far} + {frames} frames would take the run past {PHOTON_MAX_FRAMES} "
+                         "(the int32 counts of a pixel)")
+    return PhotonParams(adu, inv, fmax, ts, tt)
+
+
+def photon_shape(shape, what: str = "photons"):
+    """``(P, H, W)`` of a frame shape: 3-D as it is (the calib layout), 2-D as one panel (an image) -- or
+    ValueError.  1 <= P * H * W < 2^31."""
+    try:
+        shape = tuple(operator.index(s) for s in shape)
+    except TypeError:
+        raise ValueError(f"{what}: the shape must be a sequence of integers, got {shape!r}") from None
+    if len(shape) == 2:
+        shape = (1, *shape)
+    if len(shape) != 3 or min(shape) < 1 or shape[0] * shape[1] * shape[2] >= 2 ** 31:
+        raise ValueError(f"{what}: the shape must be [P, H, W] or [H, W] with 1 <= P * H * W < 2^31, got {shape}")
+    return shape
+
+
+def validate_photon_maps(shape, mask=None, roi=None, n_roi=None, what: str = "photons"):
+    """Host check of the keep-mask and the ROI labels (numpy arrays or CPU tensors) for frames of ``shape``.
+    Returns ``(mask uint8 [n] or None, roi uint8 [n] or None, R)``: R = ``n_roi``, or without it 1 + the
+    largest label other than 255 (1 without labels).  ValueError for a wrong size or dtype, R outside 1 .. 8,
+    several ROIs without labels, or a label >= R other than 255."""
+    P, H, W = photon_shape(shape, what)
+    n = P * H * W
+
+    def flat(a, name):
+        if a is None:
+            return None
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        if a.dtype == np.bool_:
+            a = a.astype(np.uint8)
+        if a.dtype != np.uint8:
+            raise ValueError(f"{what}: {name} is {a.dtype}, expected uint8")
+        if a.size != n:
+            raise ValueError(f"{what}: {name} of {a.size} elements for frames of {n}")
+        return np.ascontiguousarray(a.reshape(-1))
+
+    mask, roi = flat(mask, "mask"), flat(roi, "roi")
+    if n_roi is None:
+        R = 1
+        if roi is not None:
+            lab = roi[roi != PHOTON_ROI_NONE]
+            R = 1 + (int(lab.max()) if lab.size else 0)
+    else:
+        try:
+            R = operator.index(n_roi)
+        except TypeError:
+            raise ValueError(f"{what}: n_roi must be an integer, got {n_roi!r}") from None
+    if not 1 <= R <= PHOTON_MAX_ROI:
+        raise ValueError(f"{what}: {R} ROIs; 1 .. {PHOTON_MAX_ROI} are possible (labels 0 .. 7, 255 = none)")
+    if roi is None and R != 1:
+        raise ValueError(f"{what}: {R} ROIs need labels")
+    if roi is not None and bool(((roi >= R) & (roi != PHOTON_ROI_NONE)).any()):
+        raise ValueError(f"{what}: a label >= n_roi = {R} other than {PHOTON_ROI_NONE}")
+    return mask, roi, R
+
+
+def photon_count_reference(frames: torch.Tensor, shape, params, mask=None, roi=None, n_roi=None) -> PhotonCounts:
+    """K-13 golden: photons per pixel by the float32 operations of the contract, then integers.  ``frames``:
+    [F, ...] float32 of ``shape`` = [P, H, W] (or [H, W]); ``params``: a :class:`PhotonParams`, or the
+    arguments of :func:`validate_photon_params` as a tuple / dict / bare adu_per_photon.
+
+    ok = kept by the mask && v > 0 && v <= vmax; x = ok ? v * inv : 0 (one float32 multiply); w = floor(x),
+    r = x - w.  Pixel p is a seed iff r_p >= thr_seed and it beats every 4-connected neighbour of its panel
+    (r_p > r_q, or equal with p < q: padded shifts make a missing neighbour r = 0); k = w + (seed && r_p +
+    max neighbour r >= thr_total).  Returns kmap, the increments of cnt / psum / occ, and per frame pk
+    [R, 8] (pixels of ROI r with k == j + 1, the last bin k >= 8) and tot [R] (their sum of k)."""
+    what = "photons"
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.float32:
+        raise ValueError(f"{what}: frames must be a float32 tensor, got {getattr(frames, 'dtype', type(frames))}")
+    F = int(frames.shape[0]) if frames.dim() >= 1 else 0
+    if F < 1:
+        raise ValueError(f"{what}: no frames")
+    if isinstance(params, PhotonParams):
+        pp = validate_photon_params(params, frames=F, what=what)
+    elif isinstance(params, dict):
+        pp = validate_photon_params(**params, frames=F, what=what)
+    elif isinstance(params, (tuple, list)):
+        pp = validate_photon_params(*params, frames=F, what=what)
+    else:
+        pp = validate_photon_params(params, frames=F, what=what)
+    P, H, W = photon_shape(shape, what)
+    n = P * H * W
+    x = frames.detach().cpu().reshape(F, -1)
+    if x.shape[1] != n:
+        raise ValueError(f"{what}: frames of {x.shape[1]} elements for the shape {(P, H, W)}")
+    mask, roi, R = validate_photon_maps((P, H, W), mask, roi, n_roi, what)
+    inv = torch.tensor(pp.inv, dtype=torch.float32)
+    ok = (x > 0.0) & (x <= torch.tensor(pp.vmax, dtype=torch.float32))
+    if mask is not None:
+        ok &= torch.from_numpy(mask != 0)
+    scaled = torch.where(ok, x * inv, torch.zeros_like(x))     # float32
+    whole = torch.floor(scaled)
+    r = (scaled - whole).reshape(F, P, H, W)                   # exact
+    rp = torch.nn.functional.pad(r, (1, 1, 1, 1))              # zeros around every panel
+    up, down = rp[..., :-2, 1:-1], rp[..., 2:, 1:-1]
+    left, right = rp[..., 1:-1, :-2], rp[..., 1:-1, 2:]
+    seed = (r >= torch.tensor(pp.thr_seed, dtype=torch.float32)) & (r > up) & (r > left) & (r >= right) & (r >= down)
+    rmax = torch.maximum(torch.maximum(up, down), torch.maximum(left, right))
+    merge = seed & ((r + rmax) >= torch.tensor(pp.thr_total, dtype=torch.float32))
+    k = (whole.to(torch.int64) + merge.reshape(F, n).to(torch.int64))
+    pk = torch.zeros((F, R * PHOTON_PK_BINS), dtype=torch.int64)
+    tot = torch.zeros((F, R), dtype=torch.int64)
+    lab = torch.zeros(n, dtype=torch.int64) if roi is None else torch.from_numpy(roi.astype(np.int64))
+    counted = (k >= 1) & (lab < R)
+    labc = torch.where(lab < R, lab, torch.zeros_like(lab)).expand(F, n)
+    pk.scatter_add_(1, labc * PHOTON_PK_BINS + (k.clamp(1, PHOTON_PK_BINS) - 1), counted.to(torch.int64))
+    tot.scatter_add_(1, labc, torch.where(counted, k, torch.zeros_like(k)))
+    return PhotonCounts(k.to(torch.uint8), ok.sum(dim=0).to(torch.int32), k.sum(dim=0),
+                        (k >= 1).sum(dim=0).to(torch.int32), pk.reshape(F, R, PHOTON_PK_BINS).to(torch.int32), tot)

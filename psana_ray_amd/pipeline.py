@@ -17,7 +17,8 @@ radial profile (K-08) the same way and keeps an exact integer run accumulator on
 SparseFrameConsumer writes the pixels above a threshold as (index, value) pairs (K-10), optionally only
 of the frames the peak finder calls hits; PowderConsumer keeps the exact per-pixel run sums, spread and
 maximum of the calibrated frames (K-11), split into misses and hits by the same device-side filter;
-PixelHistConsumer keeps the exact per-pixel spectrum of the calibrated frames (K-12).
+PixelHistConsumer keeps the exact per-pixel spectrum of the calibrated frames (K-12); PhotonConsumer counts
+photons per pixel with psana's neighbour merge (K-13): run maps and the per-frame P(k) of up to 8 ROIs.
 """
 from __future__ import annotations
 
@@ -1377,3 +1378,161 @@ class PixelHistConsumer(_BatchConsumer):
 
         return PixelHist(self.detector, self.layout, self.shape, self.lo, self.hi, self.nbins, self.frames,
                          self.synchronize().copy())
+
+
+class PhotonConsumer(_BatchConsumer):
+    """Consumer engine: batches of leased slots -> K-13 photon counting (csrc/photons.hip) ->
+    stream-ordered release.
+
+    Per run: per pixel the samples (``cnt``), the photons (``psum``) and the frames with at least one photon
+    (``occ``); per frame and ROI the photon-count distribution ``pk`` [R, 8] and the photons ``tot`` [R] --
+    integers, so the result is exact in any frame order.  The frames never leave the GPU: the per-frame rows
+    (a few hundred bytes) go to pinned host memory stream-ordered.  The kernel owns a pixel per launch and
+    uses no global atomics on the run accumulators, so every consumer stream has its OWN set;
+    :meth:`synchronize` adds the sets on the device and copies one result to the host."""
+
+    name = "photons"
+    wants_meta = True
+
+    def __init__(self, endpoint: QueueEndpoint, frame_shape, adu_per_photon, vmax: Optional[float] = None,
+                 thr_seed: Optional[float] = None, thr_total: Optional[float] = None, mask=None, roi=None,
+                 n_roi: Optional[int] = None, detector: str = "", layout: str = "calib", batch: Optional[int] = None,
+                 stream_kind: str = CONSUMER_STREAM_KIND, streams: int = CONSUMER_STREAMS,
+                 ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
+        """frame_shape: the shape of a (calibrated) frame, [P, H, W] or [H, W].  mask / roi: uint8 arrays of
+        that many elements (keep-mask; ROI labels 0 .. R - 1, 255 = none), or None.  check_ring=False: the
+        queue carries RAW frames that the caller calibrates before :meth:`process_frames`
+        (``--calibrate_on_read``)."""
+        from .ops import reference as _ref
+
+        self.shape = tuple(int(s) for s in frame_shape)
+        self.phw = _ref.photon_shape(self.shape, "photons")
+        self.n = int(np.prod(self.phw))
+        self.params = _ref.validate_photon_params(adu_per_photon, vmax, thr_seed, thr_total, what="photons")
+        self._mask_np, self._roi_np, self.n_roi = _ref.validate_photon_maps(self.phw, mask, roi, n_roi, "photons")
+        self.max_frames = _ref.PHOTON_MAX_FRAMES
+        self.detector, self.layout = str(detector), str(layout)
+        if check_ring:
+            if endpoint.ring.dtype != torch.float32:
+                raise ValueError(f"photons: the queue carries {endpoint.ring.dtype} frames, photon counting needs "
+                                 "calibrated float32 ones")
+            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
+                raise ValueError(f"photons: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        self._host = self._new_host()
+        # per batch: (pk int32 [n, R, 8], tot int64 [n, R], [(rank, idx, gevt, photon_energy), ...]); on the GPU
+        # path the arrays are pinned host tensors filled asynchronously: valid after sync_streams()
+        self.results = []
+        if self.gpu:
+            dev, n, B, R = self.device, self.n, self.batch, self.n_roi
+            # one accumulator set per stream; set k is only ever touched by launches on stream k
+            self._acc = [(torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
+                          torch.zeros(n, dtype=torch.int32, device=dev)) for _ in self.streams]
+            self._pk = torch.zeros((self._nbuf, B, R, _ref.PHOTON_PK_BINS), dtype=torch.int32, device=dev)
+            self._tot = torch.zeros((self._nbuf, B, R), dtype=torch.int64, device=dev)
+            self._mask = None if self._mask_np is None else torch.from_numpy(self._mask_np).to(dev)
+            self._roi = None if self._roi_np is None else torch.from_numpy(self._roi_np).to(dev)
+            if self._roi is not None:
+                self._roi._pr_checked_roi = (n, R)   # validated on the host above
+
+    def _new_host(self) -> dict:
+        n = self.n
+        return {"cnt": np.zeros(n, np.int32), "psum": np.zeros(n, np.int64), "occ": np.zeros(n, np.int32)}
+
+    def _check_bound(self, n: int):
+        if self.frames + n > self.max_frames:
+            raise ValueError(f"photons: {self.frames} + {n} frames would take the run past {self.max_frames} "
+                             "(the int32 counts of a pixel)")
+
+    def _check_batch(self, n):
+        if n > self.batch:
+            raise ValueError(f"photons: {n} frames in a batch of at most {self.batch}")
+        self._check_bound(n)
+
+    def _limit(self, n_max):
+        self._check_bound(1)   # before any lease
+        return max(1, min(n_max, self.max_frames - self.frames))
+
+    def process_frames(self, frames, meta):
+        """Count ``frames`` (tensors of n elements on this consumer's device, issued on the current stream)
+        that are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank, idx, gevt,
+        photon_energy)``.  GPU: returns the consumer stream the batch runs on."""
+        return super().process_frames(frames, [tuple(m) + (None,) * (4 - len(m)) for m in meta])
+
+    def _meta_of(self, recs):
+        # a slot header carries NaN for "no photon energy", a queue item None
+        return [(r.rank, r.idx, r.gevt, None if r.photon_energy != r.photon_energy else r.photon_energy)
+                for r in recs]
+
+    def _launch_slots(self, C, slots, b, k, st):
+        P, H, W = self.phw
+        pp = self.params
+        cnt, psum, occ = self._acc[k]
+        C.photons_slots(self.ep.pool, self.ep._slot_bytes, slots, P, H, W, pp.inv, pp.vmax, pp.thr_seed, pp.thr_total,
+                        0 if self._mask is None else int(self._mask.data_ptr()),
+                        0 if self._roi is None else int(self._roi.data_ptr()), self.n_roi, int(cnt.data_ptr()),
+                        int(psum.data_ptr()), int(occ.data_ptr()), int(self._pk[b].data_ptr()),
+                        int(self._tot[b].data_ptr()), int(st.cuda_stream))
+
+    def _launch_tensors(self, frames, b, k, st):
+        n = len(frames)
+        cnt, psum, occ = self._acc[k]
+        kernels.photons([t.reshape(-1) for t in frames], self.phw, self.params, cnt, psum, occ, self._pk[b, :n],
+                        self._tot[b, :n], mask=self._mask, roi=self._roi, n_roi=self.n_roi,
+                        frames_so_far=self.frames, stream=st)
+
+    def _launched(self, b, n, st, meta):
+        """The batch's per-frame rows go to PINNED HOST memory by asynchronous copies on the current
+        (consumer) stream; the kept tensors are valid after :meth:`sync_streams`."""
+        from .ops.reference import PHOTON_PK_BINS
+
+        pk = torch.empty((n, self.n_roi, PHOTON_PK_BINS), dtype=torch.int32, pin_memory=True)
+        tot = torch.empty((n, self.n_roi), dtype=torch.int64, pin_memory=True)
+        pk.copy_(self._pk[b, :n], non_blocking=True)
+        tot.copy_(self._tot[b, :n], non_blocking=True)
+        self.results.append((pk, tot, meta))
+
+    def _reference(self, frames, meta):
+        from .ops import reference
+
+        x = torch.stack([t.reshape(-1) for t in frames])
+        out = reference.photon_count_reference(x, self.phw, self.params, self._mask_np, self._roi_np, self.n_roi)
+        self._host["cnt"] += out.cnt.numpy()
+        self._host["psum"] += out.psum.numpy()
+        self._host["occ"] += out.occ.numpy()
+        self.results.append((out.pk, out.tot, list(meta)))
+
+    def synchronize(self) -> dict:
+        """Wait for every batch, add the per-stream accumulator sets ON THE DEVICE (exact: a count of the run
+        is at most its frames, which the bound keeps inside an int32) and copy the one result to the host.
+        Returns the dict of ``cnt`` int32 / ``psum`` int64 / ``occ`` int32 [n]."""
+        if self.gpu:
+            self.sync_streams()
+            with torch.cuda.device(self.device):
+                host = {}
+                for i, name in enumerate(("cnt", "psum", "occ")):
+                    total = self._acc[0][i]
+                    if len(self._acc) > 1:
+                        total = total.clone()
+                        for acc in self._acc[1:]:
+                            total += acc[i]
+                    host[name] = total.cpu().numpy()
+                    del total
+                self._host = host
+        return self._host
+
+    def stats(self):
+        """The (synchronised) run as a :class:`psana_ray_amd.photons.PhotonStats`."""
+        from .photons import PhotonStats
+
+        h = self.synchronize()
+        meta = [m for _, _, ms in self.results for m in ms]
+        as_np = lambda t: t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)   # noqa: E731
+        R = self.n_roi
+        pk = np.concatenate([as_np(p) for p, _, _ in self.results]) if self.results else np.zeros((0, R, 8), np.int32)
+        tot = np.concatenate([as_np(t) for _, t, _ in self.results]) if self.results else np.zeros((0, R), np.int64)
+        return PhotonStats.from_maps(self.detector, self.layout, self.shape, self.params, self._mask_np, self._roi_np,
+                                     R, self.frames, h["cnt"].copy(), h["psum"].copy(), h["occ"].copy(),
+                                     rank=[m[0] for m in meta], idx=[m[1] for m in meta], gevt=[m[2] for m in meta],
+                                     photon_energy=[float("nan") if m[3] is None else float(m[3]) for m in meta],
+                                     pk=pk.copy(), tot=tot.copy())

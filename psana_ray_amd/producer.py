@@ -77,7 +77,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--data_dir", type=str, default=None, help="raw-run files directory (or $PSANA_RAY_DATA)")
     g.add_argument("--chunk", type=int, default=64, help="frames per H2D copy / kernel launch (<= 64)")
     g.add_argument("--route", type=str, default="balanced", choices=["balanced", "local_first", "spread"])
-    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder", "hist"],
+    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons"],
                    help="also consume on every producer rank (co-located consumer, BASELINE config 5): the K-07 "
                         "peak finder, the K-08 radial profile (default binning of psana-ray-consumer), the K-09 "
                         "dark statistics (needs --mode raw; --out_dark writes the file), or the K-10 zero "
@@ -85,7 +85,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "psana-ray-consumer --task sparse), or the K-11 powder statistics (--out_powder writes the "
                         "file; --powder_vmin ... --min_peaks as for psana-ray-consumer --task powder), or the K-12 "
                         "per-pixel histograms (--out_hist writes the file; --hist_lo --hist_hi --hist_bins as for "
-                        "psana-ray-consumer --task hist)")
+                        "psana-ray-consumer --task hist), or the K-13 photon counting (--out_photons writes the file; "
+                        "--adu_per_photon ... --photon_roi as for psana-ray-consumer --task photons)")
+    g.add_argument("--out_photons", type=str, default=None,
+                   help="--consumer_task photons: write the rank's photon statistics "
+                        "(psana_ray_amd.photons.PhotonStats .npz) here")
     g.add_argument("--out_hist", type=str, default=None,
                    help="--consumer_task hist: write the rank's per-pixel histograms (psana_ray_amd.hist.PixelHist "
                         ".npz) here")
@@ -123,11 +127,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "the SDMA engines (utils/runtime_env.py)")
     g.add_argument("--local", action="store_true",
                    help="single-process queue: no rendezvous; requires --consumer_task (no external consumers)")
-    from .consumer import add_hist_arguments, add_powder_arguments, add_sparse_arguments
+    from .consumer import add_hist_arguments, add_photon_arguments, add_powder_arguments, add_sparse_arguments
 
     add_sparse_arguments(parser)
     add_powder_arguments(parser)
     add_hist_arguments(parser)
+    add_photon_arguments(parser)
     return parser
 
 
@@ -257,7 +262,7 @@ def main(argv=None) -> int:
     from .models import RadialBinning, make_geometry
     from .models.detector import Mode
     from .parallel.launch import bind_numa_to_device, detect, device_for
-    from .pipeline import (DarkStatsConsumer, PeakFinderConsumer, PixelHistConsumer, PowderConsumer,
+    from .pipeline import (DarkStatsConsumer, PeakFinderConsumer, PhotonConsumer, PixelHistConsumer, PowderConsumer,
                            ProducerPipeline, RadialProfileConsumer, SparseFrameConsumer)
     from .queue.endpoint import EndOfStream, QueueEndpoint
     from .queue.ring import FrameRing, physical_slots
@@ -291,7 +296,7 @@ def main(argv=None) -> int:
                       "or a co-located --consumer_task")
             return 2
         mode = Mode.raw   # frames travel raw; DataReader applies read_mode
-    if args.consumer_task in ("radial", "sparse", "powder", "hist") and (mode == Mode.raw or int(args.panel_shards) > 1):
+    if args.consumer_task in ("radial", "sparse", "powder", "hist", "photons") and (mode == Mode.raw or int(args.panel_shards) > 1):
         log.error("--consumer_task %s needs whole calibrated frames (not --mode raw / --panel_shards)",
                   args.consumer_task)
         return 2
@@ -299,10 +304,13 @@ def main(argv=None) -> int:
         log.error("--consumer_task dark needs whole raw frames (--mode raw, no --panel_shards)")
         return 2
     for flag, task in (("out_sparse", "sparse"), ("out_dark", "dark"), ("out_powder", "powder"),
-                       ("out_hist", "hist")):
+                       ("out_hist", "hist"), ("out_photons", "photons")):
         if getattr(args, flag) is not None and args.consumer_task != task:
             log.error("--%s belongs to --consumer_task %s", flag, task)
             return 2
+    if args.consumer_task == "photons" and args.adu_per_photon is None:
+        log.error("--consumer_task photons needs --adu_per_photon")
+        return 2
     shards = int(args.panel_shards)
     if shards > 1:
         from .source.shard import PanelShardSource, shard_layout
@@ -424,7 +432,7 @@ def main(argv=None) -> int:
             # consumer thread, at the end of the stream), report(result or None, frames consumed) after the join
             each = None
 
-            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder / .hist merge)
+            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder / .hist / .photons merge)
                 root, ext = os.path.splitext(path)
                 return path if size == 1 else f"{root}.r{rank}{ext}"
 
@@ -511,6 +519,26 @@ def main(argv=None) -> int:
                         path = rank_path(args.out_hist)
                         ph.save(path)
                         log.info("Rank %d: pixel histograms written to %s", rank, path)
+            elif args.consumer_task == "photons":
+                try:
+                    from .consumer import load_photon_maps
+
+                    pmask, proi = load_photon_maps(args, frame_shape)
+                    cons = PhotonConsumer(ep, frame_shape, args.adu_per_photon, vmax=args.photon_vmax,
+                                          thr_seed=args.photon_seed, thr_total=args.photon_total, mask=pmask,
+                                          roi=proi, detector=args.detector_name, layout=mode.value)
+                except (ValueError, OSError) as e:
+                    log.error("--consumer_task photons: %s", e)
+                    return 2
+                finish = cons.stats
+
+                def report(st, consumed):
+                    print(f"Consumer {rank} photons: frames={0 if st is None else st.frames} "
+                          f"photons={0 if st is None else int(st.psum.sum())}", flush=True)
+                    if st is not None and args.out_photons:
+                        path = rank_path(args.out_photons)
+                        st.save(path)
+                        log.info("Rank %d: photon statistics written to %s", rank, path)
             else:
                 cons = PeakFinderConsumer(ep, frame_shape, PeakFinderParams())
                 finish = cons.synchronize
