@@ -489,6 +489,80 @@ def main(argv=None):
                     "rounds_us_per_frame": us(ts),
                     "bytes_vs_read_floor": round(nbytes / fbytes, 3), "vs_read_floor": round(mh[0] / mr[0], 3),
                     "vs_powder": round(mh[0] / mp[0], 3), "TB_per_s": round(nbytes / mh[0] / 1e12, 3)}, frames=FR)
+    if want("droplets"):
+        # K-14 droplets: 64 SEPARATELY allocated float32 frames per launch, with the read floor and sparsify (same
+        # window, cap = pix_cap) on the SAME frames in the same process -- alternating rounds, the median round of
+        # each.  Input: the synthetic photon background of the photons row (Poisson(0.02) photons of 10.0 per pixel
+        # plus Gaussian noise of 1.0).  Three thresholds: 3.0 (photons and their rare noise neighbours), and the
+        # quantiles of the batch that make about 1 % and 5 % of the pixels active (the last deep in the noise:
+        # ragged random clusters).  pix_cap = cap = n // 16, so that no case overflows.  The phases are timed one by
+        # one on the scratch block a full launch just filled.
+        FR, rounds, adu = 64, 5, 10.0
+        C = _ext.load()
+        gen = torch.Generator(device=dev).manual_seed(13)
+        shape3 = spec.frame_shape if len(spec.frame_shape) == 3 else (1, *spec.frame_shape)
+        rate = torch.full((npix,), 0.02, device=dev)
+        dfl = [(torch.poisson(rate, generator=gen) + 0.1 * torch.randn(npix, generator=gen, device=dev)) * adu
+               for _ in range(FR)]
+        sample = torch.cat([t[::16] for t in dfl]).sort().values
+        cases = [("photon background", 3.0, 5.0)]
+        for q in (0.01, 0.05):
+            thr = float(sample[int(sample.numel() * (1.0 - q))])
+            cases.append((f"{q:.0%} active", thr, thr))
+        capp = capd = npix // 16
+        nact = torch.zeros(FR, dtype=torch.int32, device=dev)
+        ndrop = torch.zeros(FR, dtype=torch.int32, device=dev)
+        flg = torch.zeros(FR, dtype=torch.uint8, device=dev)
+        offs = torch.zeros(FR + 1, dtype=torch.int64, device=dev)
+        i32 = lambda: torch.empty(FR * capd, dtype=torch.int32, device=dev)   # noqa: E731
+        i64 = lambda: torch.empty(FR * capd, dtype=torch.int64, device=dev)   # noqa: E731
+        cols = (i32(), i32(), i64(), i64(), i64(), i32())
+        scr = torch.empty(kernels.droplets_scratch_bytes(npix, capp, capd, FR), dtype=torch.uint8, device=dev)
+        spix = torch.empty(FR * capp, dtype=torch.int32, device=dev)
+        sval = torch.empty(FR * capp, dtype=torch.float32, device=dev)
+        sscr = torch.empty(kernels.sparsify_scratch_bytes(npix, capp, FR), dtype=torch.uint8, device=dev)
+        sums = torch.zeros(FR, dtype=torch.float32, device=dev)
+        fp64 = [int(t.data_ptr()) for t in dfl]
+
+        def dr_fn(k, phases=15):
+            _, lo, seed = cases[k]
+            return lambda: kernels.droplets(dfl, shape3, dict(thr_low=lo, thr_seed=seed), capp, capd, nact, ndrop, flg,
+                                            offs, *cols, scratch=scr, _phases=phases)
+
+        def sp_fn(k):
+            return lambda: kernels.sparsify(dfl, cases[k][1], 2.0 ** 20, capp, nact, flg, offs, spix, sval, scratch=sscr)
+
+        t_read, t_sp, t_dr = [], {k: [] for k in range(len(cases))}, {k: [] for k in range(len(cases))}
+        for _ in range(rounds):
+            t_read.append(timeit(lambda: C.read_f32(fp64, npix, 16, False, int(sums.data_ptr()), _ext.stream_handle()),
+                                 a.iters))
+            for k in t_dr:
+                t_sp[k].append(timeit(sp_fn(k), a.iters))
+                t_dr[k].append(timeit(dr_fn(k), a.iters))
+        med = lambda ts: sorted(ts)[rounds // 2]   # noqa: E731
+        us = lambda ts: [round(t[0] * 1e6 / FR, 3) for t in ts]   # noqa: E731
+        mr = med(t_read)
+        fbytes = FR * npix * 4
+        report("read_f32 reference (K=16)", mr, fbytes, {"rounds_us_per_frame": us(t_read)}, frames=FR)
+        for k, (name, lo, seed) in enumerate(cases):
+            dr_fn(k)()
+            torch.cuda.synchronize()
+            active, drops, stored = int(nact.sum()), int(ndrop.sum()), int(offs[FR])
+            over = int((flg != 0).sum())
+            phase = {}
+            for pname, bit in (("scan", 1), ("index_link", 2), ("reduce", 4), ("count_pack", 8)):
+                dr_fn(k)()   # a full launch leaves the state every phase starts from
+                phase[pname + "_us_per_frame"] = round(timeit(dr_fn(k, bit), a.iters)[0] * 1e6 / FR, 3)
+            ms, md = med(t_sp[k]), med(t_dr[k])
+            report(f"sparsify({name})", ms, fbytes + active * 16,
+                   {"thr": round(lo, 3), "cap": capp, "density": round(active / (FR * npix), 6),
+                    "rounds_us_per_frame": us(t_sp[k]), "vs_read_floor": round(ms[0] / mr[0], 3)}, frames=FR)
+            report(f"droplets({name})", md, fbytes + active * 16,
+                   {"thr_low": round(lo, 3), "thr_seed": round(seed, 3), "pix_cap": capp, "cap": capd,
+                    "density": round(active / (FR * npix), 6), "droplets_per_frame": round(drops / FR, 1),
+                    "droplets_stored": stored, "frames_overflowed": over, "scratch_bytes": scr.numel(), **phase,
+                    "rounds_us_per_frame": us(t_dr[k]), "vs_read_floor": round(md[0] / mr[0], 3),
+                    "vs_sparsify": round(md[0] / ms[0], 3)}, frames=FR)
     if want("h2d"):
         C = _ext.load()
         hp = src.pool

@@ -99,7 +99,7 @@ static FramePtrs make_ptrs(const std::vector<uint64_t>& in, const std::vector<ui
 }
 
 // The consumers' ring-slot bindings (peakfind_slots, radial_slots, dark_slots, sparsify_slots,
-// powder_slots, pixel_hist_slots, photons_slots): the two
+// powder_slots, pixel_hist_slots, photons_slots, droplets_slots): the two
 // checks they share, then fn(index of the chunk's first slot, its slot pointers) for every chunk of at
 // most kMaxFrames slots.
 template <class Fn>
@@ -491,6 +491,44 @@ PYBIND11_MODULE(_C, m) {
   m.def("photons_block_pixels", &pr::photons_block_pixels, py::arg("W"),
         "consecutive pixels one block of lanes of the K-13 kernel owns at this panel width");
   m.def("photons_max_grid", &pr::photons_max_grid, "workgroups of the K-13 kernel at most");
+
+  m.def("droplets",
+        [](const std::vector<uint64_t>& in, int P, int H, int W, float thr_low, float thr_seed, float vmax, int frac_bits,
+           int64_t cap_pix, int64_t cap, uint64_t mask, uint64_t nact, uint64_t ndrop, uint64_t flags, uint64_t offs,
+           uint64_t label, uint64_t npix, uint64_t adu, uint64_t sy, uint64_t sx, uint64_t qmax, uint64_t scratch,
+           int64_t scratch_bytes, uint64_t stream, int phases) {
+          pr::launch_droplets(make_ptrs(in, in), (int)in.size(), P, H, W, thr_low, thr_seed, vmax, frac_bits, cap_pix, cap,
+                              mask, nact, ndrop, flags, offs, label, npix, adu, sy, sx, qmax, scratch, scratch_bytes,
+                              stream, phases);
+        },
+        py::arg("in_ptrs"), py::arg("P"), py::arg("H"), py::arg("W"), py::arg("thr_low"), py::arg("thr_seed"),
+        py::arg("vmax"), py::arg("frac_bits"), py::arg("cap_pix"), py::arg("cap"), py::arg("mask"), py::arg("nact"),
+        py::arg("ndrop"), py::arg("flags"), py::arg("offs"), py::arg("label"), py::arg("npix"), py::arg("adu"),
+        py::arg("sy"), py::arg("sx"), py::arg("qmax"), py::arg("scratch"), py::arg("scratch_bytes"), py::arg("stream"),
+        py::arg("phases") = 15,
+        "K-14 droplets of up to 64 float32 frames [P, H, W]: nact / ndrop / flags / offs and the six droplet columns");
+  m.def("droplets_scratch_bytes", &pr::droplets_scratch_bytes, py::arg("n"), py::arg("cap_pix"), py::arg("cap"),
+        py::arg("frames"));
+  // consumer hot path: ring slots -> droplet batch (K-10 scan, index, link, reduce, count, pack), one native call
+  m.def("droplets_slots",
+        [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int P, int H, int W, float thr_low,
+           float thr_seed, float vmax, int frac_bits, int64_t cap_pix, int64_t cap, uint64_t mask, uint64_t nact,
+           uint64_t ndrop, uint64_t flags, uint64_t offs, uint64_t label, uint64_t npix, uint64_t adu, uint64_t sy,
+           uint64_t sx, uint64_t qmax, uint64_t scratch, int64_t scratch_bytes, uint64_t stream) {
+          const int ns = (int)slots.size();   // one launch: the batch's offs and columns are packed together
+          pr::check(ns >= 1 && ns <= pr::kMaxFrames, "droplets_slots: 1..64 slots per batch");
+          for_slot_chunks(pool, slot_bytes, slots, (int64_t)P * H * W * 4, "droplets_slots",
+                          [&](int, const std::vector<uint64_t>& in) {
+                            pr::launch_droplets(make_ptrs(in, in), (int)in.size(), P, H, W, thr_low, thr_seed, vmax,
+                                                frac_bits, cap_pix, cap, mask, nact, ndrop, flags, offs, label, npix, adu,
+                                                sy, sx, qmax, scratch, scratch_bytes, stream);
+                          });
+        },
+        py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("P"), py::arg("H"), py::arg("W"),
+        py::arg("thr_low"), py::arg("thr_seed"), py::arg("vmax"), py::arg("frac_bits"), py::arg("cap_pix"),
+        py::arg("cap"), py::arg("mask"), py::arg("nact"), py::arg("ndrop"), py::arg("flags"), py::arg("offs"),
+        py::arg("label"), py::arg("npix"), py::arg("adu"), py::arg("sy"), py::arg("sx"), py::arg("qmax"),
+        py::arg("scratch"), py::arg("scratch_bytes"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
 
   m.def("copy_h2d_kernel",
         [](uint64_t dst, uint64_t src, int64_t bytes, int workgroups, uint64_t stream) {

@@ -122,4 +122,17 @@ void launch_photons(const FramePtrs& fp, int nframes, int P, int H, int W, float
                     float thr_total, uint64_t mask, uint64_t roi, int n_roi, uint64_t kmap, uint64_t cnt,
                     uint64_t psum, uint64_t occ, uint64_t pk, uint64_t tot, uint64_t stream,
                     int variant = 0);   // measurements only: bit 0 = 2 frames in flight, bits 8.. = grid cap
+// K-14 droplets (csrc/droplets.hip): the 4-connected clusters of the pixels of up to kMaxFrames float32 frames
+// of shape [P, H, W] that the mask keeps and whose value lies in [thr_low, vmax], kept when a pixel reaches
+// thr_seed.  Writes nact / ndrop int32 [F], flags uint8 [F] (bit 0 = ndrop > cap, bit 2 = nact > cap_pix; either
+// stores nothing), offs int64 [F + 1] and the columns label / npix / qmax int32, adu / sy / sx int64 of F * cap
+// rows: frame f's droplets at offs[f] .. offs[f + 1], label ascending.  The first launch is K-10's scan and
+// pack (launch_sparsify) into the scratch block of droplets_scratch_bytes(n, cap_pix, cap, F) bytes, owned by
+// one stream; no launch after it reads a frame.  One call is complete in itself: nothing needs clearing.
+int64_t droplets_scratch_bytes(int64_t n, int64_t cap_pix, int64_t cap, int frames);
+void launch_droplets(const FramePtrs& fp, int nframes, int P, int H, int W, float thr_low, float thr_seed, float vmax,
+                     int frac_bits, int64_t cap_pix, int64_t cap, uint64_t mask, uint64_t nact, uint64_t ndrop,
+                     uint64_t flags, uint64_t offs, uint64_t label, uint64_t npix, uint64_t adu, uint64_t sy, uint64_t sx,
+                     uint64_t qmax, uint64_t scratch, int64_t scratch_bytes, uint64_t stream,
+                     int phases = 15);   // measurements only: 1 = scan, 2 = index + link, 4 = reduce, 8 = count + pack
 }  // namespace pr

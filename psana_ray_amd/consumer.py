@@ -15,11 +15,13 @@ at least ``--min_peaks`` peaks), ``powder`` (on-GPU K-11 powder statistics: exac
 spread, maximum and count above a threshold of the calibrated frames, misses and hits apart with
 ``--min_peaks``), ``hist`` (on-GPU K-12 per-pixel histograms: the exact spectrum of every pixel of the
 calibrated frames, for gain maps), ``photons`` (on-GPU K-13 photon counting: photons per pixel with psana's
-neighbour merge, run maps and the per-frame P(k) of up to 8 ROIs) or ``none``.  ``--out`` writes the peak lists / the radial accumulator / the dark
+neighbour merge, run maps and the per-frame P(k) of up to 8 ROIs), ``droplets`` (on-GPU K-14 connected-pixel
+clusters of every frame: label, pixel count, summed charge and centre of mass as integers) or ``none``.  ``--out`` writes the peak lists / the radial accumulator / the dark
 statistics / the sparse frames / the powder statistics to an ``.npz`` (several consumers' radial files add
 with ``psana_ray_amd.radial.merge``, dark files with ``psana_ray_amd.dark.merge``, sparse files join with
 ``psana_ray_amd.sparse.merge``, powder files merge with ``psana_ray_amd.powder.merge``, histogram files with
-``psana_ray_amd.hist.merge``, photon files with ``psana_ray_amd.photons.merge``).
+``psana_ray_amd.hist.merge``, photon files with ``psana_ray_amd.photons.merge``, droplet files with
+``psana_ray_amd.droplets.merge``).
 """
 from __future__ import annotations
 
@@ -44,14 +46,15 @@ def build_parser():
     ap.add_argument("--ray_namespace", type=str, default=DEFAULT_RAY_NAMESPACE)
     ap.add_argument("--queue_name", type=str, default=DEFAULT_QUEUE_NAME)
     ap.add_argument("--device", type=str, default=None)
-    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "train", "none"],
+    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets", "train", "none"],
                     help="train: online PeakNetLite training from peak-finder labels (trainer.py); radial: radial "
                          "profile I(r) / I(q) of every frame + run accumulator (--nbins ... --radial_mask); dark: "
                          "per-pixel dark-run statistics of a RAW queue (--adu_min / --adu_max); sparse: zero-suppressed "
                          "frames to disk (--sparse_thr ... --min_peaks); powder: per-pixel run sums / spread / max of the "
                          "calibrated frames, misses and hits apart (--powder_vmin ... --min_peaks); hist: per-pixel "
                          "histograms of the calibrated frames (--hist_lo --hist_hi --hist_bins); photons: photons per pixel "
-                         "of the calibrated frames (--adu_per_photon ... --photon_roi)")
+                         "of the calibrated frames (--adu_per_photon ... --photon_roi); droplets: connected clusters of "
+                         "pixels above a threshold per frame (--drop_thr_low ... --drop_mask)")
     ap.add_argument("--lr", type=float, default=1e-3, help="--task train: AdamW learning rate")
     ap.add_argument("--save", type=str, default=None, help="--task train: write the model state_dict here")
     ap.add_argument("--ddp", action="store_true",
@@ -72,7 +75,8 @@ def build_parser():
                          "the sparse frames (psana_ray_amd.sparse.SparseFrames npz) when --task sparse; the powder "
                          "statistics (psana_ray_amd.powder.PowderStats npz) when --task powder; the per-pixel histograms "
                          "(psana_ray_amd.hist.PixelHist npz) when --task hist; the photon statistics "
-                         "(psana_ray_amd.photons.PhotonStats npz) when --task photons")
+                         "(psana_ray_amd.photons.PhotonStats npz) when --task photons; the droplet lists "
+                         "(psana_ray_amd.droplets.DropletFrames npz) when --task droplets")
     g = ap.add_argument_group("--task radial")
     g.add_argument("--nbins", type=int, default=512, help="radial bins (1 .. 4096)")
     g.add_argument("--center", type=str, default=None, help="beam centre Y,X in image pixels (default: image centre)")
@@ -94,6 +98,7 @@ def build_parser():
     add_powder_arguments(ap)
     add_hist_arguments(ap)
     add_photon_arguments(ap)
+    add_droplet_arguments(ap)
     ap.add_argument("--timeout", type=float, default=300.0)
     ap.add_argument("--metrics_interval", type=float, default=10.0, help="seconds between rate lines; 0 disables")
     ap.add_argument("--metrics_json", type=str, default=None, help="append per-interval metrics as JSON lines")
@@ -162,6 +167,63 @@ def add_photon_arguments(ap):
     g.add_argument("--photon_roi", type=str, default=None,
                    help=".npy uint8 ROI labels of the frames' shape: 0 .. 7, 255 = in no ROI (default: one ROI of "
                         "every pixel); P(k) and the photon total are kept per frame and ROI")
+
+
+def add_droplet_arguments(ap):
+    """The flags of ``--task droplets`` (the producer CLI's ``--consumer_task droplets`` takes the same)."""
+    g = ap.add_argument_group("--task droplets")
+    g.add_argument("--drop_thr_low", type=float, default=None,
+                   help="a pixel is active with thr_low <= value <= vmax (required for the task)")
+    g.add_argument("--drop_thr_seed", type=float, default=None,
+                   help="a cluster is kept when one of its pixels reaches this (default: thr_low)")
+    g.add_argument("--drop_vmax", type=float, default=float(2 ** 20),
+                   help="pixels above are inactive and split a cluster (default 2^20)")
+    g.add_argument("--drop_frac_bits", type=int, default=2,
+                   help="charge is summed as round(v * 2^S), S in 0 .. 16 (default 2); vmax * 2^S must stay below 2^31")
+    g.add_argument("--drop_pix_cap", type=int, default=None,
+                   help="active pixels per frame at most (default n // 16); a frame with more is not labelled and is "
+                        "flagged")
+    g.add_argument("--drop_cap", type=int, default=None,
+                   help="droplets per frame at most (default n // 64); a frame with more stores nothing and is flagged")
+    g.add_argument("--drop_mask", type=str, default=None,
+                   help=".npy keep-mask of the frames' shape: non-zero = keep (default: every pixel)")
+
+
+def load_droplet_mask(path, shape):
+    """``--drop_mask``: a uint8 keep-mask [n] of the frames' shape (an image may come without its leading axis of
+    1), or None; ValueError for another shape."""
+    import numpy as np
+
+    if not path:
+        return None
+    mask = np.load(path)   # allow_pickle stays False
+    shape = tuple(shape)
+    if tuple(mask.shape) != shape and not (shape[0] == 1 and tuple(mask.shape) == shape[1:]):
+        raise ValueError(f"--drop_mask is {tuple(mask.shape)}, the frames are {shape}")
+    return (mask != 0).astype(np.uint8).reshape(-1)
+
+
+def droplet_consumer(args, endpoint, shape, name, layout, check_ring=True):
+    """The DropletConsumer of ``--task droplets`` / ``--consumer_task droplets`` from the ``--drop_*`` flags."""
+    from .pipeline import DropletConsumer
+
+    return DropletConsumer(endpoint, shape, args.drop_thr_low, thr_seed=args.drop_thr_seed, vmax=args.drop_vmax,
+                           frac_bits=args.drop_frac_bits, pix_cap=args.drop_pix_cap, cap=args.drop_cap,
+                           mask=load_droplet_mask(args.drop_mask, shape), detector=name, layout=layout,
+                           batch=args.batch, check_ring=check_ring)
+
+
+def droplet_start_line(cid, cons) -> str:
+    pp = cons.params
+    return (f"Consumer {cid} droplets: thr_low={pp.thr_low:g} thr_seed={pp.thr_seed:g} vmax={pp.vmax:g} "
+            f"frac_bits={pp.frac_bits} pix_cap={cons.pix_cap} cap={cons.cap} batch={cons.batch} "
+            f"scratch_bytes={cons.scratch_bytes} x {max(1, len(cons.streams))}")
+
+
+def droplet_final_line(cid, cons, name, layout) -> str:
+    m = cons.metrics()
+    return (f"Consumer {cid} droplets: frames={cons.frames} detector={name} layout={layout} "
+            f"stored={m['frames_stored']} droplets={m['droplets_stored']} overflowed={m['frames_overflowed']}")
 
 
 def load_photon_maps(args, shape):
@@ -636,8 +698,45 @@ def run_photons(args, reader, stop, progress) -> int:
     return rc
 
 
+def run_droplets(args, reader, stop, progress) -> int:
+    """--task droplets: find droplets until the end of the stream; ``progress["n"]`` counts frames."""
+    from . import droplets
+
+    cid = reader.consumer_id
+    if not _has_whole_frames(reader, "droplets", "droplets"):
+        return 2
+    cal = reader.calibrator
+    try:
+        name, layout, shape = sparse_layout(reader, args, needs="droplets need")
+    except ValueError as e:
+        log.error("--task droplets: %s", e)
+        return 2
+    if not name:
+        log.error("--task droplets: the session does not name its detector; pass --detector_name")
+        return 2
+    try:
+        cons = droplet_consumer(args, reader.endpoint, shape, name, layout, check_ring=cal is None)
+    except (ValueError, KeyError, OSError) as e:
+        log.error("--task droplets: %s", e)
+        return 2
+    print(droplet_start_line(cid, cons), flush=True)
+    held = []
+    rc = _drive(args, reader, stop, progress, cons,
+                raw_meta=None if cal is None else lambda it: (it.rank, it.idx, it.gevt, it.photon_energy),
+                each=lambda: held.extend(cons.take_results()))
+    cons.synchronize()
+    held.extend(cons.take_results())
+    print(droplet_final_line(cid, cons, name, layout), flush=True)
+    if args.out:
+        droplets.concat(held or [cons.empty()]).save(args.out)
+    return rc
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
+    if args.task == "droplets" and args.drop_thr_low is None:
+        print("psana-ray-consumer: --task droplets needs --drop_thr_low", file=sys.stderr)
+        return 2
     if args.task == "photons" and args.adu_per_photon is None:
         print("psana-ray-consumer: --task photons needs --adu_per_photon", file=sys.stderr)
         return 2
@@ -676,7 +775,7 @@ def main(argv=None) -> int:
                             json_path=args.metrics_json).start()
         pf = None
         run_task = {"radial": run_radial, "dark": run_dark, "sparse": run_sparse, "powder": run_powder,
-                    "hist": run_hist, "photons": run_photons}.get(args.task)
+                    "hist": run_hist, "photons": run_photons, "droplets": run_droplets}.get(args.task)
         if run_task is not None:   # the tasks that run a pipeline consumer to the end of the stream
             progress = {"n": 0}
             registry.register(args.task, lambda: {"frames_consumed": progress["n"]})

@@ -1,4 +1,4 @@
-"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-13).
+"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-14).
 
 Every wrapper checks device / dtype / shape / contiguity / alignment on the host BEFORE the
 launch (a mis-shaped launch of a hand-written kernel can fault the GPU), splits batches into
@@ -569,6 +569,79 @@ def sparsify(frames: Sequence[torch.Tensor], thr: float, vmax: float, cap: int, 
     C.sparsify([_ptr(t) for t in frames], n, thr, vmax, cap, 0 if mask is None else _ptr(mask),
                0 if keys is None else _ptr(keys), key_min, _ptr(nnz), _ptr(flags), _ptr(offs), _ptr(pix), _ptr(val),
                _ptr(scratch), scratch.numel() * scratch.element_size(), s)
+
+
+def droplets_scratch_bytes(n: int, cap_pix: int, cap: int, frames: int) -> int:
+    """Bytes of the K-14 scratch block for batches of up to ``frames`` frames of ``n`` elements at ``cap_pix``
+    active pixels and ``cap`` droplets per frame: K-10's flags / offsets (1 KiB), the (frame, block) droplet
+    counts (8 KiB), K-10's own scratch and 52 B per row of F * cap_pix (index, value, parent, joined, qmax and the four
+    int64 accumulators).  Pure arithmetic (the extension computes the same figure;
+    the launcher checks the block against its own)."""
+    n, cap_pix, cap, frames = int(n), int(cap_pix), int(cap), int(frames)
+    if cap < 1 or frames * cap >= 2 ** 31:
+        raise ValueError("droplets_scratch_bytes: cap out of range")
+    rows = (cap_pix * frames + 3) // 4 * 4
+    return 1024 + MAX_FRAMES * 32 * 4 + (sparsify_scratch_bytes(n, cap_pix, frames) + 15) // 16 * 16 + 52 * rows
+
+
+def droplets(frames: Sequence[torch.Tensor], shape, params, cap_pix: int, cap: int, nact: torch.Tensor,
+             ndrop: torch.Tensor, flags: torch.Tensor, offs: torch.Tensor, label: torch.Tensor, npix: torch.Tensor,
+             adu: torch.Tensor, sy: torch.Tensor, sx: torch.Tensor, qmax: torch.Tensor,
+             mask: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None, stream=None, _phases: int = 15):
+    """K-14 droplets (csrc/droplets.hip; contract: ops.reference.droplet_reference).
+    frames: F (1 .. 64) float32 tensors of ``shape`` = [P, H, W] (or [H, W]) on one GPU.  ``params``: a
+    ``DropletParams`` or the arguments of ``validate_droplet_params``.  Outputs (overwritten, no clearing
+    needed): nact / ndrop int32 [F], flags uint8 [F] (bit 0 ndrop > cap, bit 2 nact > cap_pix), offs int64
+    [F + 1], and the columns label / npix / qmax int32 and adu / sy / sx int64 of at least F * cap elements --
+    frame f's droplets at offs[f] .. offs[f + 1], label ascending; elements from offs[F] on are unspecified.
+    ``mask``: uint8 [n], non-zero = keep.  ``scratch``: a contiguous, 16-B aligned tensor of at least
+    droplets_scratch_bytes(n, cap_pix, cap, F) bytes that no other launch in flight uses (allocated here when
+    None; never needs clearing).  Everything is checked here, before any launch."""
+    from .reference import _droplet_params, photon_shape, validate_droplet_caps
+
+    what = "droplets"
+    F = len(frames)
+    if not 1 <= F <= MAX_FRAMES:
+        raise ValueError(f"{what}: 1 .. {MAX_FRAMES} frames per launch, got {F}")
+    P, H, W = photon_shape(shape, what)
+    pp = _droplet_params(params, what)
+    cap_pix, cap = validate_droplet_caps((P, H, W), pp, cap_pix, cap, F, what)
+    if not isinstance(frames[0], torch.Tensor):
+        raise ValueError(f"{what}: frames must be tensors")
+    dev = frames[0].device
+    n = P * H * W
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: frames on {dev}, expected a GPU")
+    _check_frames(frames, torch.float32, n, dev, f"{what} in")
+    for t, dt, k, name in ((nact, torch.int32, F, "nact"), (ndrop, torch.int32, F, "ndrop"),
+                           (flags, torch.uint8, F, "flags"), (offs, torch.int64, F + 1, "offs")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.shape != (k,) or t.device != dev \
+                or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous {dt} [{k}] tensor on {dev}")
+    for t, dt, name in ((label, torch.int32, "label"), (npix, torch.int32, "npix"), (adu, torch.int64, "adu"),
+                        (sy, torch.int64, "sy"), (sx, torch.int64, "sx"), (qmax, torch.int32, "qmax")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() < F * cap or t.device != dev \
+                or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous {dt} tensor of at least F * cap = {F * cap} "
+                             f"elements on {dev}")
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.numel() != n
+                             or mask.device != dev or not mask.is_contiguous() or _ptr(mask) % 4):
+        raise ValueError(f"{what}: mask must be a contiguous, 4-B aligned uint8 [{n}] tensor on {dev}")
+    need = droplets_scratch_bytes(n, cap_pix, cap, F)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not isinstance(scratch, torch.Tensor) or scratch.device != dev or not scratch.is_contiguous() \
+            or _ptr(scratch) % 16 or scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"{what}: scratch must be a contiguous, 16-B aligned tensor of at least {need} bytes "
+                         f"on {dev} (droplets_scratch_bytes)")
+    C = _ext.load()
+    if C.droplets_scratch_bytes(n, cap_pix, cap, F) != need:
+        raise RuntimeError("droplets: droplets_scratch_bytes disagrees with the extension")
+    s = _ext.stream_handle(stream)
+    C.droplets([_ptr(t) for t in frames], P, H, W, pp.thr_low, pp.thr_seed, pp.vmax, pp.frac_bits, cap_pix, cap,
+               0 if mask is None else _ptr(mask), _ptr(nact), _ptr(ndrop), _ptr(flags), _ptr(offs), _ptr(label),
+               _ptr(npix), _ptr(adu), _ptr(sy), _ptr(sx), _ptr(qmax), _ptr(scratch),
+               scratch.numel() * scratch.element_size(), s, int(_phases))
 
 
 def mask_frames(frames: Sequence[torch.Tensor], zero: torch.Tensor, stream=None):

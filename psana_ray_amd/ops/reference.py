@@ -709,3 +709,210 @@ def photon_count_reference(frames: torch.Tensor, shape, params, mask=None, roi=N
     tot.scatter_add_(1, labc, torch.where(counted, k, torch.zeros_like(k)))
     return PhotonCounts(k.to(torch.uint8), ok.sum(dim=0).to(torch.int32), k.sum(dim=0),
                         (k >= 1).sum(dim=0).to(torch.int32), pk.reshape(F, R, PHOTON_PK_BINS).to(torch.int32), tot)
+
+
+# ---- K-14 droplets ---------------------------------------------------------------------------------------------
+DROPLET_MAX_FRAMES = 64
+DROPLET_VMAX = float(2 ** 20)        # the K-08 window's upper end
+DROPLET_FRAC_BITS = 2
+DROPLET_MAX_FRAC_BITS = 16
+DROPLET_PIX_CAP_DIV = 16             # default cap_pix = n // 16 active pixels per frame
+DROPLET_CAP_DIV = 64                 # default cap = n // 64 droplets per frame
+DROPLET_FLAG_OVERFLOW = 1            # ndrop[f] > cap: the frame stores nothing
+DROPLET_FLAG_PIX_OVERFLOW = 4        # nact[f] > cap_pix: the frame is not labelled, ndrop[f] = 0
+
+
+class DropletParams(NamedTuple):
+    """The validated parameters of K-14 as the kernel sees them (every float a float32 value)."""
+    thr_low: float
+    thr_seed: float
+    vmax: float
+    frac_bits: int
+    qlim: int           # Q = ceil(vmax * 2^frac_bits) < 2^31: no q is larger
+
+
+class DropletList(NamedTuple):
+    """What :func:`droplet_reference` returns: every output of one launch (columns cut at offs[F])."""
+    nact: torch.Tensor    # int32 [F]
+    ndrop: torch.Tensor   # int32 [F]
+    flags: torch.Tensor   # uint8 [F]
+    offs: torch.Tensor    # int64 [F + 1]
+    label: torch.Tensor   # int32 [offs[F]]
+    npix: torch.Tensor    # int32
+    adu: torch.Tensor     # int64
+    sy: torch.Tensor      # int64
+    sx: torch.Tensor      # int64
+    qmax: torch.Tensor    # int32
+
+
+def validate_droplet_params(thr_low, thr_seed=None, vmax=None, frac_bits=None, what: str = "droplets") -> DropletParams:
+    """The parameters as float32 values with Q = ceil(vmax * 2^frac_bits) -- or ValueError.  ``thr_seed`` None:
+    thr_low; ``vmax`` None: 2^20; ``frac_bits`` None: 2.  Requires finite 0 < thr_low <= thr_seed <= vmax,
+    frac_bits in 0 .. 16 and Q < 2^31."""
+    if isinstance(thr_low, DropletParams):
+        thr_low, thr_seed, vmax, frac_bits, _q = thr_low
+    try:
+        with np.errstate(over="ignore", under="ignore"):
+            lo = float(np.float32(thr_low))
+            seed = lo if thr_seed is None else float(np.float32(thr_seed))
+            hi = float(np.float32(DROPLET_VMAX if vmax is None else vmax))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: thr_low, thr_seed and vmax must be numbers") from None
+    try:
+        S = operator.index(DROPLET_FRAC_BITS if frac_bits is None else frac_bits)
+    except TypeError:
+        raise ValueError(f"{what}: frac_bits must be an integer, got {frac_bits!r}") from None
+    if not (np.isfinite(lo) and np.isfinite(seed) and np.isfinite(hi)):
+        raise ValueError(f"{what}: thr_low, thr_seed and vmax must be finite float32 values, got {thr_low}, {thr_seed}, "
+                         f"{vmax}")
+    if not 0.0 < lo <= seed <= hi:
+        raise ValueError(f"{what}: need 0 < thr_low <= thr_seed <= vmax, got {lo}, {seed}, {hi}")
+    if not 0 <= S <= DROPLET_MAX_FRAC_BITS:
+        raise ValueError(f"{what}: frac_bits must be 0 .. {DROPLET_MAX_FRAC_BITS}, got {S}")
+    q = int(np.ceil(hi * float(2 ** S)))    # exact in float64: a float32 value times a power of two
+    if q >= 2 ** 31:
+        raise ValueError(f"{what}: ceil(vmax * 2^frac_bits) = {q} must be below 2^31 (q and qmax are int32)")
+    return DropletParams(lo, seed, hi, S, q)
+
+
+def _droplet_params(params, what: str = "droplets") -> DropletParams:
+    if isinstance(params, DropletParams):
+        return validate_droplet_params(params, what=what)
+    if isinstance(params, dict):
+        return validate_droplet_params(**params, what=what)
+    if isinstance(params, (tuple, list)):
+        return validate_droplet_params(*params, what=what)
+    return validate_droplet_params(params, what=what)
+
+
+def validate_droplet_caps(shape, params, cap_pix=None, cap=None, frames: int = 1, what: str = "droplets"):
+    """``(cap_pix, cap)`` as Python ints -- defaults max(1, n // 16) and max(1, n // 64) -- or ValueError: both
+    >= 1 with F * cap_pix < 2^31 and F * cap < 2^31, 1 <= F <= 64, and
+    Q * (max(H, W) - 1) * min(H * W, cap_pix) <= 2^63 - 1, so that no sum of a stored droplet can wrap."""
+    P, H, W = photon_shape(shape, what)
+    pp = _droplet_params(params, what)
+    n = P * H * W
+    try:
+        F = operator.index(frames)
+        cap_pix = max(1, n // DROPLET_PIX_CAP_DIV) if cap_pix is None else operator.index(cap_pix)
+        cap = max(1, n // DROPLET_CAP_DIV) if cap is None else operator.index(cap)
+    except TypeError:
+        raise ValueError(f"{what}: cap_pix, cap and the frame count must be integers") from None
+    if not 1 <= F <= DROPLET_MAX_FRAMES:
+        raise ValueError(f"{what}: 1 .. {DROPLET_MAX_FRAMES} frames per launch, got {F}")
+    if cap_pix < 1 or F * cap_pix >= 2 ** 31:
+        raise ValueError(f"{what}: cap_pix must be >= 1 with F * cap_pix < 2^31, got {cap_pix} for {F} frames")
+    if cap < 1 or F * cap >= 2 ** 31:
+        raise ValueError(f"{what}: cap must be >= 1 with F * cap < 2^31, got {cap} for {F} frames")
+    if pp.qlim * (max(H, W) - 1) * min(H * W, cap_pix) > 2 ** 63 - 1:
+        raise ValueError(f"{what}: Q * (max(H, W) - 1) * min(H * W, cap_pix) = {pp.qlim} * {max(H, W) - 1} * "
+                         f"{min(H * W, cap_pix)} passes 2^63 - 1: lower vmax, frac_bits or cap_pix")
+    return cap_pix, cap
+
+
+def droplet_mask(shape, mask, what: str = "droplets"):
+    """The keep-mask as a contiguous numpy uint8 [n] (bool accepted), or None -- or ValueError."""
+    P, H, W = photon_shape(shape, what)
+    if mask is None:
+        return None
+    m = mask.detach().cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
+    if m.dtype == np.bool_:
+        m = m.astype(np.uint8)
+    if m.dtype != np.uint8 or m.size != P * H * W:
+        raise ValueError(f"{what}: mask must be uint8 of {P * H * W} elements, got {m.dtype} of {m.size}")
+    return np.ascontiguousarray(m.reshape(-1))
+
+
+def droplet_reference(frames: torch.Tensor, shape, params, mask=None, cap_pix=None, cap=None) -> DropletList:
+    """K-14 golden: droplets of every frame.  ``frames``: [F, ...] float32 of ``shape`` = [P, H, W] (or [H, W]),
+    1 <= F <= 64; ``params``: a :class:`DropletParams`, or the arguments of :func:`validate_droplet_params` as a
+    tuple / dict / bare thr_low.
+
+    A pixel is active iff the mask keeps it and thr_low <= v <= vmax (float32 compares).  Labels come from
+    iterated minimum propagation over the four in-panel neighbours with pointer jumping: every active pixel ends
+    with the lowest linear index of its 4-connected set.  A set is kept iff one of its pixels has v >= thr_seed.
+    q = int64(rint(v * 2^S)) (float32 multiply, ties to even); npix, adu = sum q, sy / sx = sum q * row / column,
+    qmax per kept set, in ascending label order.  A frame with nact > cap_pix has ndrop 0 and flag bit 2; one
+    with ndrop > cap has flag bit 0; either stores nothing."""
+    what = "droplets"
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.float32:
+        raise ValueError(f"{what}: frames must be a float32 tensor, got {getattr(frames, 'dtype', type(frames))}")
+    F = int(frames.shape[0]) if frames.dim() >= 1 else 0
+    if F < 1:
+        raise ValueError(f"{what}: no frames")
+    pp = _droplet_params(params, what)
+    P, H, W = photon_shape(shape, what)
+    n = P * H * W
+    cap_pix, cap = validate_droplet_caps((P, H, W), pp, cap_pix, cap, F, what)
+    x = frames.detach().cpu().reshape(F, -1).numpy()
+    if x.shape[1] != n:
+        raise ValueError(f"{what}: frames of {x.shape[1]} elements for the shape {(P, H, W)}")
+    m = droplet_mask((P, H, W), mask, what)
+    with np.errstate(invalid="ignore"):
+        act = (x >= np.float32(pp.thr_low)) & (x <= np.float32(pp.vmax))
+    if m is not None:
+        act &= (m != 0)[None, :]
+    # minimum propagation: lab = lowest index seen so far, n where inactive
+    idx = np.arange(n, dtype=np.int64)
+    lab = np.where(act, idx[None, :], n)
+    a4 = act.reshape(F, P, H, W)
+    while True:
+        l4 = lab.reshape(F, P, H, W)
+        pad = np.full((F, P, H + 2, W + 2), n, dtype=np.int64)
+        pad[:, :, 1:-1, 1:-1] = l4
+        nb = np.minimum(np.minimum(pad[:, :, :-2, 1:-1], pad[:, :, 2:, 1:-1]),
+                        np.minimum(pad[:, :, 1:-1, :-2], pad[:, :, 1:-1, 2:]))
+        new = np.where(a4, np.minimum(l4, nb), n).reshape(F, n)
+        # pointer jumping: the label is a pixel of the same set, whose label is no larger
+        ext = np.concatenate([new, np.full((F, 1), n, dtype=np.int64)], axis=1)
+        for _ in range(4):
+            ext[:, :n] = np.take_along_axis(ext, ext[:, :n], axis=1)
+        new = ext[:, :n]
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    scale = np.float32(2 ** pp.frac_bits)
+    nact = act.sum(axis=1).astype(np.int64)
+    ndrop = np.zeros(F, dtype=np.int64)
+    flags = np.zeros(F, dtype=np.uint8)
+    offs = np.zeros(F + 1, dtype=np.int64)
+    cols = {k: [] for k in ("label", "npix", "adu", "sy", "sx", "qmax")}
+    for f in range(F):
+        stored = 0
+        if nact[f] > cap_pix:
+            flags[f] |= DROPLET_FLAG_PIX_OVERFLOW
+        else:
+            ai = np.nonzero(act[f])[0]
+            v = x[f, ai]
+            roots, inv = np.unique(lab[f, ai], return_inverse=True)   # ascending
+            seeded = np.zeros(roots.size, dtype=bool)
+            np.logical_or.at(seeded, inv, v >= np.float32(pp.thr_seed))
+            ndrop[f] = int(seeded.sum())
+            if ndrop[f] > cap:
+                flags[f] |= DROPLET_FLAG_OVERFLOW
+            else:
+                stored = int(ndrop[f])
+                q = np.rint(v * scale).astype(np.int64)
+                r = ai % (H * W)
+                yy, xx = r // W, r % W
+                k = roots.size
+
+                def red(w):
+                    out = np.zeros(k, dtype=np.int64)
+                    np.add.at(out, inv, w)
+                    return out[seeded]
+
+                qm = np.zeros(k, dtype=np.int64)
+                np.maximum.at(qm, inv, q)
+                cols["label"].append(roots[seeded].astype(np.int32))
+                cols["npix"].append(red(np.ones_like(q)).astype(np.int32))
+                cols["adu"].append(red(q))
+                cols["sy"].append(red(q * yy))
+                cols["sx"].append(red(q * xx))
+                cols["qmax"].append(qm[seeded].astype(np.int32))
+        offs[f + 1] = offs[f] + stored
+    dt = {"label": np.int32, "npix": np.int32, "adu": np.int64, "sy": np.int64, "sx": np.int64, "qmax": np.int32}
+    out = {k: torch.from_numpy(np.concatenate(v) if v else np.zeros(0, dtype=dt[k])) for k, v in cols.items()}
+    return DropletList(torch.from_numpy(nact.astype(np.int32)), torch.from_numpy(ndrop.astype(np.int32)),
+                       torch.from_numpy(flags), torch.from_numpy(offs), out["label"], out["npix"], out["adu"], out["sy"],
+                       out["sx"], out["qmax"])

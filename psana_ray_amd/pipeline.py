@@ -18,7 +18,8 @@ SparseFrameConsumer writes the pixels above a threshold as (index, value) pairs 
 of the frames the peak finder calls hits; PowderConsumer keeps the exact per-pixel run sums, spread and
 maximum of the calibrated frames (K-11), split into misses and hits by the same device-side filter;
 PixelHistConsumer keeps the exact per-pixel spectrum of the calibrated frames (K-12); PhotonConsumer counts
-photons per pixel with psana's neighbour merge (K-13): run maps and the per-frame P(k) of up to 8 ROIs.
+photons per pixel with psana's neighbour merge (K-13): run maps and the per-frame P(k) of up to 8 ROIs;
+DropletConsumer writes every frame's connected clusters of pixels above a threshold as integer rows (K-14).
 """
 from __future__ import annotations
 
@@ -1536,3 +1537,213 @@ class PhotonConsumer(_BatchConsumer):
                                      rank=[m[0] for m in meta], idx=[m[1] for m in meta], gevt=[m[2] for m in meta],
                                      photon_energy=[float("nan") if m[3] is None else float(m[3]) for m in meta],
                                      pk=pk.copy(), tot=tot.copy())
+
+
+class DropletConsumer(_BatchConsumer):
+    """Consumer engine: batches of leased slots -> K-14 droplets (csrc/droplets.hip) -> stream-ordered release.
+
+    Per frame: the 4-connected clusters of pixels with ``thr_low <= v <= vmax`` (and ``mask != 0``) that hold a
+    pixel ``v >= thr_seed``, each as integers (label, npix, adu, sy, sx, qmax), label ascending; at most
+    ``pix_cap`` active pixels and ``cap`` droplets per frame (a frame with more stores nothing and is flagged).
+    Results reach the host through pinned buffers in two steps per batch, as SparseFrameConsumer's do: the
+    header (offs, nact, ndrop, flags) first, then exactly ``offs[F]`` rows of the six columns; the wait for a
+    batch's header happens after the NEXT batch (on the other stream) has been issued.  Finished batches collect
+    in :attr:`results` as :class:`psana_ray_amd.droplets.DropletFrames`.  Only the first launch of a batch (K-10's
+    scan) reads frame values, so the ring slots go back stream-ordered right after the native call.  One scratch
+    block and one output set per stream; a batch that would not fit the free HBM share is lowered, not refused."""
+
+    name = "droplets"
+    wants_meta = True
+    _COLS = (("label", torch.int32), ("npix", torch.int32), ("adu", torch.int64), ("sy", torch.int64),
+             ("sx", torch.int64), ("qmax", torch.int32))
+
+    def __init__(self, endpoint: QueueEndpoint, frame_shape, thr_low, thr_seed: Optional[float] = None,
+                 vmax: Optional[float] = None, frac_bits: Optional[int] = None, pix_cap: Optional[int] = None,
+                 cap: Optional[int] = None, mask=None, detector: str = "", layout: str = "calib",
+                 batch: Optional[int] = None, stream_kind: str = CONSUMER_STREAM_KIND, streams: int = CONSUMER_STREAMS,
+                 ranks_per_gpu: Optional[int] = None, check_ring: bool = True, hbm_budget: Optional[int] = None):
+        """frame_shape: the shape of a (calibrated) frame, [P, H, W] or [H, W].  mask: uint8 keep-mask of that many
+        elements, or None.  check_ring=False: the queue carries RAW frames that the caller calibrates before
+        :meth:`process_frames` (``--calibrate_on_read``).  hbm_budget: bytes this consumer's scratch blocks and
+        outputs may take (None: half of the free device memory divided by the ranks sharing the GPU)."""
+        from . import droplets as _dr
+        from .ops import reference as _ref
+
+        self.shape = tuple(int(s) for s in frame_shape)
+        self.phw = _ref.photon_shape(self.shape, "droplets")
+        self.n = int(np.prod(self.phw))
+        self.params = _ref.validate_droplet_params(thr_low, thr_seed, vmax, frac_bits, what="droplets")
+        self._mask_np = _ref.droplet_mask(self.phw, mask, "droplets")
+        self.mask_sha256 = _dr.mask_hash(self.phw, self._mask_np)
+        self.detector, self.layout = str(detector), str(layout)
+        if check_ring:
+            if endpoint.ring.dtype != torch.float32:
+                raise ValueError(f"droplets: the queue carries {endpoint.ring.dtype} frames, droplets need "
+                                 "calibrated float32 ones")
+            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
+                raise ValueError(f"droplets: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        self.pix_cap, self.cap = _ref.validate_droplet_caps(self.phw, self.params, pix_cap, cap, self.batch, "droplets")
+        self.frames_stored = self.frames_overflowed = self.droplets_stored = 0
+        self.results = []      # finished batches (DropletFrames), oldest first
+        self._pending = collections.deque()   # GPU batches in flight: dicts, oldest first
+        self._lock = threading.Lock()
+        self.scratch_bytes = 0
+        if self.gpu:
+            dev, ns = self.device, len(self.streams)
+            if hbm_budget is None:
+                if ranks_per_gpu is None:
+                    from .parallel.launch import ranks_per_gpu as _rpg
+
+                    ranks_per_gpu = _rpg()
+                hbm_budget = torch.cuda.mem_get_info(dev)[0] // 2 // max(1, int(ranks_per_gpu))
+
+            def need(B):   # scratch per stream + the output rows
+                return ns * kernels.droplets_scratch_bytes(self.n, self.pix_cap, self.cap, B) \
+                    + self._nbuf * B * self.cap * 36
+
+            asked = self.batch
+            while self.batch > 1 and need(self.batch) > hbm_budget:
+                self.batch = (self.batch + 1) // 2
+            if self.batch != asked:
+                log.warning("droplets: a batch of %d frames needs %.1f MB, the HBM share is %.1f MB: batch lowered to %d",
+                            asked, need(asked) / 1e6, hbm_budget / 1e6, self.batch)
+            B = self.batch
+            self.scratch_bytes = kernels.droplets_scratch_bytes(self.n, self.pix_cap, self.cap, B)
+            log.info("droplets: %d scratch block(s) of %.1f MB (52 B per row of %d x %d active pixels), outputs %.1f MB",
+                     ns, self.scratch_bytes / 1e6, B, self.pix_cap, self._nbuf * B * self.cap * 36 / 1e6)
+            # header of a batch in ONE row: offs int64 [B + 1] | nact int32 [B] | ndrop int32 [B] | flags uint8 [B]
+            self._hdr_bytes = 8 * (B + 1) + 9 * B
+            self._hdr = torch.zeros((self._nbuf, (self._hdr_bytes + 15) // 16 * 16), dtype=torch.uint8, device=dev)
+            self._hdr_host = torch.zeros(self._hdr.shape, dtype=torch.uint8, pin_memory=True)
+            self._out = {k: torch.empty((self._nbuf, B * self.cap), dtype=dt, device=dev) for k, dt in self._COLS}
+            # one scratch block per stream (a block must never serve two launches in flight)
+            self._scratch = [torch.empty(self.scratch_bytes, dtype=torch.uint8, device=dev) for _ in self.streams]
+            self._mask = None if self._mask_np is None else torch.from_numpy(self._mask_np).to(dev)
+
+    # ------------------------------------------------------------------ buffers
+    def _split(self, row, n: int):
+        """(offs [n + 1], nact [n], ndrop [n], flags [n]) views of a header row (device tensor or numpy)."""
+        B = self.batch
+        i64, i32 = (torch.int64, torch.int32) if isinstance(row, torch.Tensor) else (np.int64, np.int32)
+        o = 8 * (B + 1)
+        return (row[:o].view(i64)[:n + 1], row[o:o + 4 * B].view(i32)[:n], row[o + 4 * B:o + 8 * B].view(i32)[:n],
+                row[o + 8 * B:self._hdr_bytes][:n])
+
+    def _droplet_frames(self, meta, nact, ndrop, flags, offs, cols):
+        from .droplets import DropletFrames
+
+        return DropletFrames(self.detector, self.layout, self.phw, self.params.thr_low, self.params.thr_seed,
+                             self.params.vmax, self.params.frac_bits, self.pix_cap, self.cap, self.mask_sha256,
+                             rank=[m[0] for m in meta], idx=[m[1] for m in meta], gevt=[m[2] for m in meta],
+                             photon_energy=[float("nan") if m[3] is None else float(m[3]) for m in meta],
+                             nact=nact, ndrop=ndrop, flags=flags, offs=offs, **cols)
+
+    def empty(self):
+        """A DropletFrames of no frames with this consumer's parameters (what a run without frames writes)."""
+        return self._droplet_frames([], np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8),
+                                    np.zeros(1, np.int64), {k: np.zeros(0) for k, _ in self._COLS})
+
+    def _count(self, df):
+        over = int((df.flags != 0).sum())
+        with self._lock:
+            self.frames_overflowed += over
+            self.frames_stored += len(df) - over
+            self.droplets_stored += int(df.offs[-1])
+            self.results.append(df)
+
+    # ------------------------------------------------------------------ the two host steps of a GPU batch
+    def _launched(self, b: int, n: int, st, meta):
+        """Batch just launched on ``st`` (current stream): header -> pinned host, then advance the older batches."""
+        self._hdr_host[b].copy_(self._hdr[b], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(st)
+        self._pending.append({"b": b, "n": n, "st": st, "meta": meta, "hdr": ev, "data": None})
+        self._advance(keep=1)
+
+    def _advance(self, keep: int):
+        """Step every batch but the newest ``keep``: a batch whose header is awaited gets its data copy issued; a
+        batch whose data copy was issued is collected once at least one newer batch is behind it (or on a
+        flush, keep = 0)."""
+        for i, p in enumerate(list(self._pending)):
+            if len(self._pending) - i <= keep:
+                break
+            if p["data"] is None:
+                p["hdr"].synchronize()
+                offs, nact, ndrop, flags = self._split(self._hdr_host[p["b"]].numpy(), p["n"])
+                p["offs"], p["nact"], p["ndrop"], p["flags"] = offs.copy(), nact.copy(), ndrop.copy(), flags.copy()
+                total = int(p["offs"][p["n"]])
+                p["cols"] = {k: torch.empty(total, dtype=dt, pin_memory=total > 0) for k, dt in self._COLS}
+                ev = torch.cuda.Event()
+                with torch.cuda.stream(p["st"]):   # exactly offs[F] rows, never the full capacity
+                    if total:
+                        for k, _ in self._COLS:
+                            p["cols"][k].copy_(self._out[k][p["b"], :total], non_blocking=True)
+                    ev.record(p["st"])
+                p["data"] = ev
+        while self._pending and self._pending[0]["data"] is not None and len(self._pending) > 2 * keep:
+            p = self._pending.popleft()
+            p["data"].synchronize()
+            self._count(self._droplet_frames(p["meta"], p["nact"], p["ndrop"], p["flags"], p["offs"],
+                                             {k: v.numpy().copy() for k, v in p["cols"].items()}))
+
+    # ------------------------------------------------------------------ processing
+    def process_frames(self, frames, meta):
+        """Find the droplets of ``frames`` (tensors of n elements on this consumer's device, issued on the current
+        stream) that are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank, idx, gevt,
+        photon_energy)``.  GPU: returns the consumer stream the batch runs on."""
+        return super().process_frames(frames, [tuple(m) + (None,) * (4 - len(m)) for m in meta])
+
+    def _check_batch(self, n):
+        if n > self.batch:
+            raise ValueError(f"droplets: {n} frames in a batch of at most {self.batch}")
+
+    def _meta_of(self, recs):
+        # a slot header carries NaN for "no photon energy", a queue item None
+        return [(r.rank, r.idx, r.gevt, None if r.photon_energy != r.photon_energy else r.photon_energy)
+                for r in recs]
+
+    def _launch_slots(self, C, slots, b, k, st):
+        offs, nact, ndrop, flags = self._split(self._hdr[b], len(slots))
+        P, H, W = self.phw
+        pp = self.params
+        o = self._out
+        C.droplets_slots(self.ep.pool, self.ep._slot_bytes, slots, P, H, W, pp.thr_low, pp.thr_seed, pp.vmax, pp.frac_bits,
+                         self.pix_cap, self.cap, 0 if self._mask is None else int(self._mask.data_ptr()),
+                         int(nact.data_ptr()), int(ndrop.data_ptr()), int(flags.data_ptr()), int(offs.data_ptr()),
+                         int(o["label"][b].data_ptr()), int(o["npix"][b].data_ptr()), int(o["adu"][b].data_ptr()),
+                         int(o["sy"][b].data_ptr()), int(o["sx"][b].data_ptr()), int(o["qmax"][b].data_ptr()),
+                         int(self._scratch[k].data_ptr()), self._scratch[k].numel(), int(st.cuda_stream))
+
+    def _launch_tensors(self, frames, b, k, st):
+        offs, nact, ndrop, flags = self._split(self._hdr[b], len(frames))
+        o = self._out
+        kernels.droplets([t.reshape(-1) for t in frames], self.phw, self.params, self.pix_cap, self.cap, nact, ndrop, flags,
+                         offs, o["label"][b], o["npix"][b], o["adu"][b], o["sy"][b], o["sx"][b], o["qmax"][b],
+                         mask=self._mask, scratch=self._scratch[k], stream=st)
+
+    def _reference(self, frames, meta):
+        from .ops import reference
+
+        x = torch.stack([t.reshape(-1) for t in frames])
+        r = reference.droplet_reference(x, self.phw, self.params, self._mask_np, self.pix_cap, self.cap)
+        self._count(self._droplet_frames(meta, r.nact.numpy(), r.ndrop.numpy(), r.flags.numpy(), r.offs.numpy(),
+                                         {k: getattr(r, k).numpy() for k, _ in self._COLS}))
+
+    def take_results(self) -> list:
+        """The finished batches collected so far (oldest first); they are removed from :attr:`results`."""
+        with self._lock:
+            out, self.results = self.results, []
+        return out
+
+    def metrics(self) -> dict:
+        return {"frames_consumed": self.frames, "frames_stored": self.frames_stored,
+                "frames_overflowed": self.frames_overflowed, "droplets_stored": self.droplets_stored}
+
+    def synchronize(self):
+        """Wait for every batch and collect it.  Returns the list of finished batches not taken yet."""
+        if self.gpu:
+            self._advance(keep=0)
+            self._advance(keep=0)   # first pass issues the last data copies, second collects them
+            self.sync_streams()
+        return self.results

@@ -77,7 +77,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--data_dir", type=str, default=None, help="raw-run files directory (or $PSANA_RAY_DATA)")
     g.add_argument("--chunk", type=int, default=64, help="frames per H2D copy / kernel launch (<= 64)")
     g.add_argument("--route", type=str, default="balanced", choices=["balanced", "local_first", "spread"])
-    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons"],
+    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets"],
                    help="also consume on every producer rank (co-located consumer, BASELINE config 5): the K-07 "
                         "peak finder, the K-08 radial profile (default binning of psana-ray-consumer), the K-09 "
                         "dark statistics (needs --mode raw; --out_dark writes the file), or the K-10 zero "
@@ -86,7 +86,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "file; --powder_vmin ... --min_peaks as for psana-ray-consumer --task powder), or the K-12 "
                         "per-pixel histograms (--out_hist writes the file; --hist_lo --hist_hi --hist_bins as for "
                         "psana-ray-consumer --task hist), or the K-13 photon counting (--out_photons writes the file; "
-                        "--adu_per_photon ... --photon_roi as for psana-ray-consumer --task photons)")
+                        "--adu_per_photon ... --photon_roi as for psana-ray-consumer --task photons), or the K-14 "
+                        "droplets (--out_droplets writes the file; --drop_thr_low ... --drop_mask as for "
+                        "psana-ray-consumer --task droplets)")
+    g.add_argument("--out_droplets", type=str, default=None,
+                   help="--consumer_task droplets: write the rank's droplet lists "
+                        "(psana_ray_amd.droplets.DropletFrames .npz) here")
     g.add_argument("--out_photons", type=str, default=None,
                    help="--consumer_task photons: write the rank's photon statistics "
                         "(psana_ray_amd.photons.PhotonStats .npz) here")
@@ -127,12 +132,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "the SDMA engines (utils/runtime_env.py)")
     g.add_argument("--local", action="store_true",
                    help="single-process queue: no rendezvous; requires --consumer_task (no external consumers)")
-    from .consumer import add_hist_arguments, add_photon_arguments, add_powder_arguments, add_sparse_arguments
+    from .consumer import (add_droplet_arguments, add_hist_arguments, add_photon_arguments, add_powder_arguments,
+                           add_sparse_arguments)
 
     add_sparse_arguments(parser)
     add_powder_arguments(parser)
     add_hist_arguments(parser)
     add_photon_arguments(parser)
+    add_droplet_arguments(parser)
     return parser
 
 
@@ -296,7 +303,7 @@ def main(argv=None) -> int:
                       "or a co-located --consumer_task")
             return 2
         mode = Mode.raw   # frames travel raw; DataReader applies read_mode
-    if args.consumer_task in ("radial", "sparse", "powder", "hist", "photons") and (mode == Mode.raw or int(args.panel_shards) > 1):
+    if args.consumer_task in ("radial", "sparse", "powder", "hist", "photons", "droplets") and (mode == Mode.raw or int(args.panel_shards) > 1):
         log.error("--consumer_task %s needs whole calibrated frames (not --mode raw / --panel_shards)",
                   args.consumer_task)
         return 2
@@ -304,12 +311,15 @@ def main(argv=None) -> int:
         log.error("--consumer_task dark needs whole raw frames (--mode raw, no --panel_shards)")
         return 2
     for flag, task in (("out_sparse", "sparse"), ("out_dark", "dark"), ("out_powder", "powder"),
-                       ("out_hist", "hist"), ("out_photons", "photons")):
+                       ("out_hist", "hist"), ("out_photons", "photons"), ("out_droplets", "droplets")):
         if getattr(args, flag) is not None and args.consumer_task != task:
             log.error("--%s belongs to --consumer_task %s", flag, task)
             return 2
     if args.consumer_task == "photons" and args.adu_per_photon is None:
         log.error("--consumer_task photons needs --adu_per_photon")
+        return 2
+    if args.consumer_task == "droplets" and args.drop_thr_low is None:
+        log.error("--consumer_task droplets needs --drop_thr_low")
         return 2
     shards = int(args.panel_shards)
     if shards > 1:
@@ -432,7 +442,7 @@ def main(argv=None) -> int:
             # consumer thread, at the end of the stream), report(result or None, frames consumed) after the join
             each = None
 
-            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder / .hist / .photons merge)
+            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder / .hist / .photons / .droplets merge)
                 root, ext = os.path.splitext(path)
                 return path if size == 1 else f"{root}.r{rank}{ext}"
 
@@ -539,6 +549,33 @@ def main(argv=None) -> int:
                         path = rank_path(args.out_photons)
                         st.save(path)
                         log.info("Rank %d: photon statistics written to %s", rank, path)
+            elif args.consumer_task == "droplets":
+                try:
+                    from . import droplets as _droplets
+                    from .consumer import droplet_consumer, droplet_final_line, droplet_start_line
+
+                    args.batch = None   # config.pipeline_shape, as for the other co-located consumers
+                    cons = droplet_consumer(args, ep, frame_shape, args.detector_name, mode.value)
+                except (ValueError, OSError) as e:
+                    log.error("--consumer_task droplets: %s", e)
+                    return 2
+                print(droplet_start_line(rank, cons), flush=True)
+                dheld = []
+
+                def each():
+                    dheld.extend(cons.take_results())
+
+                def finish():
+                    cons.synchronize()
+                    each()
+                    return _droplets.concat(dheld or [cons.empty()])
+
+                def report(df, consumed):
+                    print(droplet_final_line(rank, cons, args.detector_name, mode.value), flush=True)
+                    if df is not None and args.out_droplets:
+                        path = rank_path(args.out_droplets)
+                        df.save(path)
+                        log.info("Rank %d: droplet lists written to %s", rank, path)
             else:
                 cons = PeakFinderConsumer(ep, frame_shape, PeakFinderParams())
                 finish = cons.synchronize
