@@ -563,6 +563,71 @@ def main(argv=None):
                     "droplets_stored": stored, "frames_overflowed": over, "scratch_bytes": scr.numel(), **phase,
                     "rounds_us_per_frame": us(t_dr[k]), "vs_read_floor": round(md[0] / mr[0], 3),
                     "vs_sparsify": round(md[0] / ms[0], 3)}, frames=FR)
+    if want("cube"):
+        # K-15 cube: 64 SEPARATELY allocated calib frames into nbins = 64 accumulator planes, the batch's frames
+        # spread over G = 1, 2, 8, 64 bins (G = 64: every frame in a bin of its own, a delay scan with jitter),
+        # alternating in the same process with the read floor and powder(NC=1) on the SAME frames -- the median
+        # round of each.  Bytes: 4 B per pixel and frame plus one read-modify-write of the 20 B per pixel of
+        # every bin with a frame in the batch: 4 n F + 2 * 20 n G (1.16x the floor's bytes at G = 1, 11x at 64).
+        from psana_ray_amd.ops.reference import (POWDER_FRAC_BITS, POWDER_QMAX_NONE, POWDER_THR_ABOVE, POWDER_VMAX,
+                                                 POWDER_VMIN)
+
+        FR, rounds, NB = 64, 5, 64
+        C = _ext.load()
+        craw = [pool[i % pool.shape[0]].to(dev).clone() for i in range(FR)]
+        cfl = [torch.empty(spec.frame_shape, dtype=torch.float32, device=dev) for _ in range(FR)]
+        cal.run(craw, cfl)
+        torch.cuda.synchronize()
+        del craw
+        cflat = [t.reshape(-1) for t in cfl]
+        fp64 = [int(t.data_ptr()) for t in cfl]
+        sums = torch.zeros(FR, dtype=torch.float32, device=dev)
+        pacc = (torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros((1, npix), dtype=torch.int32, device=dev),
+                torch.zeros((1, npix), dtype=torch.int64, device=dev), torch.zeros((1, npix), dtype=torch.int64, device=dev),
+                torch.full((1, npix), POWDER_QMAX_NONE, dtype=torch.int32, device=dev),
+                torch.zeros((1, npix), dtype=torch.int32, device=dev))
+        cacc = (torch.zeros(NB, dtype=torch.int64, device=dev), torch.zeros((NB, npix), dtype=torch.int32, device=dev),
+                torch.zeros((NB, npix), dtype=torch.int64, device=dev),
+                torch.zeros((NB, npix), dtype=torch.int64, device=dev))
+        groups = (1, 2, 8, 64)
+        cbins = [[(f % G) * (NB // G) for f in range(FR)] for G in groups]
+
+        def reset(acc, fills):   # every timed window starts a run (it stays far below max_frames)
+            for t, v in zip(acc, fills):
+                t.fill_(v)
+
+        def cb(k):
+            return lambda: kernels.cube_accumulate(cflat, cbins[k], NB, POWDER_VMIN, POWDER_VMAX, POWDER_FRAC_BITS,
+                                                   *cacc)
+
+        t_read, t_pow, t_cube = [], [], [[] for _ in groups]
+        for _ in range(rounds):
+            t_read.append(timeit(lambda: C.read_f32(fp64, npix, 16, False, int(sums.data_ptr()), _ext.stream_handle()),
+                                 a.iters))
+            reset(pacc, (0, 0, 0, 0, POWDER_QMAX_NONE, 0))
+            t_pow.append(timeit(lambda: kernels.powder_accumulate(cflat, POWDER_VMIN, POWDER_VMAX, POWDER_FRAC_BITS,
+                                                                  POWDER_THR_ABOVE, *pacc), a.iters))
+            for k in range(len(groups)):
+                reset(cacc, (0, 0, 0, 0))
+                t_cube[k].append(timeit(cb(k), a.iters))
+        med = lambda ts: sorted(ts)[rounds // 2]   # noqa: E731
+        us = lambda ts: [round(t[0] * 1e6 / FR, 3) for t in ts]   # noqa: E731
+        mr, mp = med(t_read), med(t_pow)
+        fbytes = FR * npix * 4
+        report("read_f32 reference (K=16)", mr, fbytes, {"rounds_us_per_frame": us(t_read)}, frames=FR)
+        report("powder(NC=1)", mp, fbytes + npix * 56,
+               {"rounds_us_per_frame": us(t_pow), "bytes_vs_read_floor": round((fbytes + npix * 56) / fbytes, 3),
+                "vs_read_floor": round(mp[0] / mr[0], 3)}, frames=FR)
+        m1 = med(t_cube[0])
+        for k, G in enumerate(groups):
+            mc = med(t_cube[k])
+            nbytes = fbytes + 2 * 20 * npix * G
+            report(f"cube(G={G})", mc, nbytes,
+                   {"nbins": NB, "groups": G, "rounds_us_per_frame": us(t_cube[k]),
+                    "bytes_vs_read_floor": round(nbytes / fbytes, 3), "vs_read_floor": round(mc[0] / mr[0], 3),
+                    "vs_powder": round(mc[0] / mp[0], 3), "time_vs_G1": round(mc[0] / m1[0], 3),
+                    "bytes_vs_G1": round(nbytes / (fbytes + 40 * npix), 3),
+                    "TB_per_s": round(nbytes / mc[0] / 1e12, 3)}, frames=FR)
     if want("h2d"):
         C = _ext.load()
         hp = src.pool

@@ -99,7 +99,7 @@ static FramePtrs make_ptrs(const std::vector<uint64_t>& in, const std::vector<ui
 }
 
 // The consumers' ring-slot bindings (peakfind_slots, radial_slots, dark_slots, sparsify_slots,
-// powder_slots, pixel_hist_slots, photons_slots, droplets_slots): the two
+// powder_slots, pixel_hist_slots, photons_slots, droplets_slots, cube_slots): the two
 // checks they share, then fn(index of the chunk's first slot, its slot pointers) for every chunk of at
 // most kMaxFrames slots.
 template <class Fn>
@@ -529,6 +529,33 @@ PYBIND11_MODULE(_C, m) {
         py::arg("cap"), py::arg("mask"), py::arg("nact"), py::arg("ndrop"), py::arg("flags"), py::arg("offs"),
         py::arg("label"), py::arg("npix"), py::arg("adu"), py::arg("sy"), py::arg("sx"), py::arg("qmax"),
         py::arg("scratch"), py::arg("scratch_bytes"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+
+  m.def("cube",
+        [](const std::vector<uint64_t>& in, int64_t n, float vmin, float vmax, int frac_bits, int nbins,
+           const std::vector<int32_t>& bins, uint64_t nfr, uint64_t cnt, uint64_t sum, uint64_t sq, uint64_t stream) {
+          pr::check(bins.size() == in.size(), "cube: one bin per frame");
+          pr::launch_cube(make_ptrs(in, in), (int)in.size(), n, vmin, vmax, frac_bits, nbins, bins.data(), nfr, cnt, sum,
+                          sq, stream);
+        },
+        py::arg("in_ptrs"), py::arg("n"), py::arg("vmin"), py::arg("vmax"), py::arg("frac_bits"), py::arg("nbins"),
+        py::arg("bins"), py::arg("nfr"), py::arg("cnt"), py::arg("sum"), py::arg("sq"), py::arg("stream"),
+        "K-15 cube: adds up to 64 float32 frames into nfr [nbins] / cnt / sum / sq [nbins, n], frame f into plane "
+        "bins[f] (-1 = dropped)");
+  m.attr("CUBE_MAX_BINS") = pr::kCubeMaxBins;
+  // consumer hot path: ring slots -> cube accumulators, one native call
+  m.def("cube_slots",
+        [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int64_t n, float vmin,
+           float vmax, int frac_bits, int nbins, const std::vector<int32_t>& bins, uint64_t nfr, uint64_t cnt,
+           uint64_t sum, uint64_t sq, uint64_t stream) {
+          pr::check(bins.size() == slots.size(), "cube_slots: one bin per slot");
+          for_slot_chunks(pool, slot_bytes, slots, n * 4, "cube_slots", [&](int a, const std::vector<uint64_t>& in) {
+            pr::launch_cube(make_ptrs(in, in), (int)in.size(), n, vmin, vmax, frac_bits, nbins, bins.data() + a, nfr, cnt,
+                            sum, sq, stream);
+          });
+        },
+        py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("n"), py::arg("vmin"), py::arg("vmax"),
+        py::arg("frac_bits"), py::arg("nbins"), py::arg("bins"), py::arg("nfr"), py::arg("cnt"), py::arg("sum"),
+        py::arg("sq"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
 
   m.def("copy_h2d_kernel",
         [](uint64_t dst, uint64_t src, int64_t bytes, int workgroups, uint64_t stream) {

@@ -135,4 +135,13 @@ void launch_droplets(const FramePtrs& fp, int nframes, int P, int H, int W, floa
                      uint64_t flags, uint64_t offs, uint64_t label, uint64_t npix, uint64_t adu, uint64_t sy, uint64_t sx,
                      uint64_t qmax, uint64_t scratch, int64_t scratch_bytes, uint64_t stream,
                      int phases = 15);   // measurements only: 1 = scan, 2 = index + link, 4 = reduce, 8 = count + pack
+// K-15 cube (csrc/cube.hip): ADDS up to kMaxFrames float32 frames of n elements into the planar accumulators
+// cnt int32 / sum int64 / sq int64 [nbins, n] and nfr int64 [nbins], frame f into plane bins[f]: samples with
+// vmin <= v <= vmax, quantised as q = rintf(v * 2^frac_bits).  bins is a HOST array of nframes int32 in
+// -1 .. nbins - 1; a frame with bin -1 is dropped (not read), a bin without a frame in the launch is neither
+// read nor written, and nothing is launched when every frame is dropped.  Never clears; one owner thread per
+// pixel, so two launches in flight must not share accumulators.
+constexpr int kCubeMaxBins = 4096;
+void launch_cube(const FramePtrs& fp, int nframes, int64_t n, float vmin, float vmax, int frac_bits, int nbins,
+                 const int32_t* bins, uint64_t nfr, uint64_t cnt, uint64_t sum, uint64_t sq, uint64_t stream);
 }  // namespace pr

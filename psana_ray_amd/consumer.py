@@ -16,12 +16,14 @@ spread, maximum and count above a threshold of the calibrated frames, misses and
 ``--min_peaks``), ``hist`` (on-GPU K-12 per-pixel histograms: the exact spectrum of every pixel of the
 calibrated frames, for gain maps), ``photons`` (on-GPU K-13 photon counting: photons per pixel with psana's
 neighbour merge, run maps and the per-frame P(k) of up to 8 ROIs), ``droplets`` (on-GPU K-14 connected-pixel
-clusters of every frame: label, pixel count, summed charge and centre of mass as integers) or ``none``.  ``--out`` writes the peak lists / the radial accumulator / the dark
+clusters of every frame: label, pixel count, summed charge and centre of mass as integers), ``cube`` (on-GPU
+K-15 cube: exact per-pixel run sums of the calibrated frames per bin of the photon energy or of a per-event
+table) or ``none``.  ``--out`` writes the peak lists / the radial accumulator / the dark
 statistics / the sparse frames / the powder statistics to an ``.npz`` (several consumers' radial files add
 with ``psana_ray_amd.radial.merge``, dark files with ``psana_ray_amd.dark.merge``, sparse files join with
 ``psana_ray_amd.sparse.merge``, powder files merge with ``psana_ray_amd.powder.merge``, histogram files with
 ``psana_ray_amd.hist.merge``, photon files with ``psana_ray_amd.photons.merge``, droplet files with
-``psana_ray_amd.droplets.merge``).
+``psana_ray_amd.droplets.merge``, cube files with ``psana_ray_amd.cube.merge``).
 """
 from __future__ import annotations
 
@@ -46,7 +48,7 @@ def build_parser():
     ap.add_argument("--ray_namespace", type=str, default=DEFAULT_RAY_NAMESPACE)
     ap.add_argument("--queue_name", type=str, default=DEFAULT_QUEUE_NAME)
     ap.add_argument("--device", type=str, default=None)
-    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets", "train", "none"],
+    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets", "cube", "train", "none"],
                     help="train: online PeakNetLite training from peak-finder labels (trainer.py); radial: radial "
                          "profile I(r) / I(q) of every frame + run accumulator (--nbins ... --radial_mask); dark: "
                          "per-pixel dark-run statistics of a RAW queue (--adu_min / --adu_max); sparse: zero-suppressed "
@@ -54,7 +56,8 @@ def build_parser():
                          "calibrated frames, misses and hits apart (--powder_vmin ... --min_peaks); hist: per-pixel "
                          "histograms of the calibrated frames (--hist_lo --hist_hi --hist_bins); photons: photons per pixel "
                          "of the calibrated frames (--adu_per_photon ... --photon_roi); droplets: connected clusters of "
-                         "pixels above a threshold per frame (--drop_thr_low ... --drop_mask)")
+                         "pixels above a threshold per frame (--drop_thr_low ... --drop_mask); cube: per-pixel run sums "
+                         "per bin of the photon energy or of a per-event table (--cube_by ... --cube_frac_bits)")
     ap.add_argument("--lr", type=float, default=1e-3, help="--task train: AdamW learning rate")
     ap.add_argument("--save", type=str, default=None, help="--task train: write the model state_dict here")
     ap.add_argument("--ddp", action="store_true",
@@ -76,7 +79,8 @@ def build_parser():
                          "statistics (psana_ray_amd.powder.PowderStats npz) when --task powder; the per-pixel histograms "
                          "(psana_ray_amd.hist.PixelHist npz) when --task hist; the photon statistics "
                          "(psana_ray_amd.photons.PhotonStats npz) when --task photons; the droplet lists "
-                         "(psana_ray_amd.droplets.DropletFrames npz) when --task droplets")
+                         "(psana_ray_amd.droplets.DropletFrames npz) when --task droplets; the cube "
+                         "(psana_ray_amd.cube.CubeStats npz) when --task cube")
     g = ap.add_argument_group("--task radial")
     g.add_argument("--nbins", type=int, default=512, help="radial bins (1 .. 4096)")
     g.add_argument("--center", type=str, default=None, help="beam centre Y,X in image pixels (default: image centre)")
@@ -99,6 +103,7 @@ def build_parser():
     add_hist_arguments(ap)
     add_photon_arguments(ap)
     add_droplet_arguments(ap)
+    add_cube_arguments(ap)
     ap.add_argument("--timeout", type=float, default=300.0)
     ap.add_argument("--metrics_interval", type=float, default=10.0, help="seconds between rate lines; 0 disables")
     ap.add_argument("--metrics_json", type=str, default=None, help="append per-interval metrics as JSON lines")
@@ -187,6 +192,74 @@ def add_droplet_arguments(ap):
                    help="droplets per frame at most (default n // 64); a frame with more stores nothing and is flagged")
     g.add_argument("--drop_mask", type=str, default=None,
                    help=".npy keep-mask of the frames' shape: non-zero = keep (default: every pixel)")
+
+
+def add_cube_arguments(ap):
+    """The flags of ``--task cube`` (the producer CLI's ``--consumer_task cube`` takes the same)."""
+    g = ap.add_argument_group("--task cube")
+    g.add_argument("--cube_by", type=str, default="photon_energy", choices=["photon_energy", "gevt"],
+                   help="what bins a frame: its photon energy (--cube_edges / --cube_edges_file) or its global event "
+                        "number through a table (--cube_table)")
+    g.add_argument("--cube_edges", type=str, default=None,
+                   help="LO,HI,N: N equal energy bins, edges np.linspace(LO, HI, N + 1); frames outside are dropped")
+    g.add_argument("--cube_edges_file", type=str, default=None,
+                   help="float .npy of B + 1 strictly increasing bin edges")
+    g.add_argument("--cube_table", type=str, default=None,
+                   help="--cube_by gevt: integer 1-D .npy, table[gevt] = bin in 0 .. B - 1 or -1 (dropped); a gevt "
+                        "outside the table is dropped")
+    g.add_argument("--cube_bins", type=int, default=None,
+                   help="--cube_by gevt: the number of bins B (default: the table's largest value + 1)")
+    g.add_argument("--cube_vmin", type=float, default=-float(2 ** 20),
+                   help="value window: samples below are ignored (default -2^20)")
+    g.add_argument("--cube_vmax", type=float, default=float(2 ** 20),
+                   help="value window: samples above are ignored (default 2^20)")
+    g.add_argument("--cube_frac_bits", type=int, default=2,
+                   help="values are accumulated as round(v * 2^S), S in 0 .. 16 (default 2); max(|vmin|, |vmax|) * 2^S "
+                        "must stay below 2^31 and bounds the frames of a run (printed at start)")
+
+
+def cube_binning(args):
+    """The :class:`psana_ray_amd.cube.CubeBinning` of the ``--cube_*`` flags, or a ValueError / OSError."""
+    import numpy as np
+
+    from .cube import CubeBinning
+
+    if args.cube_by == "photon_energy":
+        if args.cube_table is not None or args.cube_bins is not None:
+            raise ValueError("--cube_table / --cube_bins belong to --cube_by gevt")
+        if args.cube_edges is not None and args.cube_edges_file is not None:
+            raise ValueError("give --cube_edges or --cube_edges_file, not both")
+        if args.cube_edges is not None:
+            parts = args.cube_edges.split(",")
+            try:
+                lo, hi, n = float(parts[0]), float(parts[1]), int(parts[2])
+                if len(parts) != 3:
+                    raise ValueError
+            except (ValueError, IndexError):
+                raise ValueError(f"--cube_edges needs LO,HI,N, got {args.cube_edges!r}") from None
+            return CubeBinning.linspace(lo, hi, n)
+        if args.cube_edges_file is not None:
+            return CubeBinning("photon_energy", edges=np.load(args.cube_edges_file, allow_pickle=False))
+        raise ValueError("no bin source: --cube_edges LO,HI,N or --cube_edges_file PATH.npy (or --cube_by gevt "
+                         "--cube_table PATH.npy)")
+    if args.cube_edges is not None or args.cube_edges_file is not None:
+        raise ValueError("--cube_edges / --cube_edges_file belong to --cube_by photon_energy")
+    if args.cube_table is None:
+        raise ValueError("no bin source: --cube_by gevt needs --cube_table PATH.npy")
+    return CubeBinning("gevt", table=np.load(args.cube_table, allow_pickle=False), nbins=args.cube_bins)
+
+
+def cube_start_line(cid, cons) -> str:
+    return (f"Consumer {cid} cube: by={cons.binning.by} bins={cons.nbins} max_frames={cons.max_frames} "
+            f"window=[{cons.vmin:g},{cons.vmax:g}] frac_bits={cons.frac_bits} set_bytes={cons.set_bytes}")
+
+
+def cube_final_line(cid, st, consumed: int) -> str:
+    if st is None:
+        return f"Consumer {cid} cube: frames={consumed} binned=0 dropped=0 bins_filled=0/0"
+    binned = int(st.frames.sum())
+    return (f"Consumer {cid} cube: frames={binned + st.dropped} binned={binned} dropped={st.dropped} "
+            f"bins_filled={int((st.frames > 0).sum())}/{st.nbins}")
 
 
 def load_droplet_mask(path, shape):
@@ -698,6 +771,43 @@ def run_photons(args, reader, stop, progress) -> int:
     return rc
 
 
+def run_cube(args, reader, stop, progress) -> int:
+    """--task cube: accumulate until the end of the stream; ``progress["n"]`` counts frames."""
+    from .pipeline import CubeConsumer
+
+    cid = reader.consumer_id
+    if not _has_whole_frames(reader, "cube", "the cube"):
+        return 2
+    cal = reader.calibrator
+    try:
+        name, layout, shape = sparse_layout(reader, args, needs="the cube needs")
+    except ValueError as e:
+        log.error("--task cube: %s", e)
+        return 2
+    if not name:
+        log.error("--task cube: the session does not name its detector; pass --detector_name")
+        return 2
+    try:
+        cons = CubeConsumer(reader.endpoint, shape, cube_binning(args), vmin=args.cube_vmin, vmax=args.cube_vmax,
+                            frac_bits=args.cube_frac_bits, detector=name, layout=layout, batch=args.batch,
+                            check_ring=cal is None)
+    except (ValueError, KeyError, OSError) as e:
+        log.error("--task cube: %s", e)
+        return 2
+    print(cube_start_line(cid, cons), flush=True)
+    try:
+        rc = _drive(args, reader, stop, progress, cons,
+                    raw_meta=None if cal is None else lambda it: (it.rank, it.idx, it.gevt, it.photon_energy))
+    except ValueError as e:   # the run reached max_frames
+        log.error("--task cube: %s", e)
+        rc = 2
+    st = cons.stats()
+    print(cube_final_line(cid, st, cons.frames), flush=True)
+    if args.out:
+        st.save(args.out)
+    return rc
+
+
 def run_droplets(args, reader, stop, progress) -> int:
     """--task droplets: find droplets until the end of the stream; ``progress["n"]`` counts frames."""
     from . import droplets
@@ -740,6 +850,12 @@ def main(argv=None) -> int:
     if args.task == "photons" and args.adu_per_photon is None:
         print("psana-ray-consumer: --task photons needs --adu_per_photon", file=sys.stderr)
         return 2
+    if args.task == "cube":   # the bin source is checked before the queue is joined
+        try:
+            cube_binning(args)
+        except (ValueError, OSError) as e:
+            print(f"psana-ray-consumer: --task cube: {e}", file=sys.stderr)
+            return 2
     logging.basicConfig(level=getattr(logging, args.log_level), format="%(asctime)s - %(levelname)s - %(message)s")
     import numpy as np
     import torch
@@ -775,7 +891,7 @@ def main(argv=None) -> int:
                             json_path=args.metrics_json).start()
         pf = None
         run_task = {"radial": run_radial, "dark": run_dark, "sparse": run_sparse, "powder": run_powder,
-                    "hist": run_hist, "photons": run_photons, "droplets": run_droplets}.get(args.task)
+                    "hist": run_hist, "photons": run_photons, "droplets": run_droplets, "cube": run_cube}.get(args.task)
         if run_task is not None:   # the tasks that run a pipeline consumer to the end of the stream
             progress = {"n": 0}
             registry.register(args.task, lambda: {"frames_consumed": progress["n"]})

@@ -1,4 +1,4 @@
-"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-14).
+"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-15).
 
 Every wrapper checks device / dtype / shape / contiguity / alignment on the host BEFORE the
 launch (a mis-shaped launch of a hand-written kernel can fault the GPU), splits batches into
@@ -348,6 +348,60 @@ def powder_accumulate(frames: Sequence[torch.Tensor], vmin: float, vmax: float, 
     for a, b in _chunks(F):
         C.powder([_ptr(t) for t in frames[a:b]], n, lo, hi, S, thr, nc, 0 if keys is None else _ptr(keys[a:b]),
                  key_min, _ptr(nfr), _ptr(cnt), _ptr(sum), _ptr(sq), _ptr(qmax), _ptr(above), s)
+
+
+def cube_accumulate(frames: Sequence[torch.Tensor], bins, nbins: int, vmin: float, vmax: float, frac_bits: int,
+                    nfr: torch.Tensor, cnt: torch.Tensor, sum: torch.Tensor, sq: torch.Tensor,
+                    frames_so_far: int = 0, stream=None):
+    """K-15 cube (csrc/cube.hip; contract: ops.reference.cube_accumulate_reference).  frames: F float32
+    tensors of n elements (any layout) on one GPU; bins: F integers on the HOST, frame f goes to bin
+    bins[f] in 0 .. nbins - 1, or is dropped (not read) with bins[f] == -1.  ADDS every sample with vmin <=
+    v <= vmax, quantised as q = round_half_even(v * 2^frac_bits), to the planar accumulators cnt int32 /
+    sum int64 / sq int64 [nbins, n] and the frames per bin to nfr int64 [nbins], on the frames' device; a
+    bin without a frame is neither read nor written.  The caller zeroes the accumulators once per run
+    and passes in ``frames_so_far`` the frames they already hold (dropped ones included): a run holds
+    at most ops.reference.powder_max_frames(vmin, vmax, frac_bits) frames.  One thread owns a pixel and
+    there are no atomics: launches in flight on DIFFERENT streams must not share accumulators.
+    Everything is checked here, before any launch."""
+    from .reference import validate_cube_bins, validate_cube_nbins, validate_powder_params
+
+    what = "cube_accumulate"
+    lo, hi, S, _thr, _Q, max_frames = validate_powder_params(vmin, vmax, frac_bits, 0.0, what)
+    nbins = validate_cube_nbins(nbins, what)
+    F = len(frames)
+    try:
+        frames_so_far = operator.index(frames_so_far)
+    except TypeError:
+        raise ValueError(f"{what}: frames_so_far must be an integer") from None
+    if frames_so_far < 0 or frames_so_far + F > max_frames:
+        raise ValueError(f"{what}: {frames_so_far} + {F} frames would take the run past max_frames = {max_frames} "
+                         "(the int32 count and the int64 sum of squares)")
+    blist = validate_cube_bins(bins, F, nbins, what)
+    if not isinstance(nfr, torch.Tensor) or nfr.dtype != torch.int64 or nfr.shape != (nbins,) \
+            or not nfr.is_contiguous() or nfr.data_ptr() % 8:
+        raise ValueError(f"{what}: nfr must be a contiguous int64 [{nbins}] tensor")
+    if F == 0:
+        return
+    if not isinstance(frames[0], torch.Tensor):
+        raise ValueError(f"{what}: frames must be tensors")
+    dev = frames[0].device
+    n = frames[0].numel()
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: frames on {dev}, expected a GPU")
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"{what}: frames must have 1 .. 2^31 - 1 elements")
+    _check_frames(frames, torch.float32, n, dev, f"{what} in")
+    if nfr.device != dev:
+        raise ValueError(f"{what}: nfr on {nfr.device}, expected {dev}")
+    for t, dt, name in ((cnt, torch.int32, "cnt"), (sum, torch.int64, "sum"), (sq, torch.int64, "sq")):
+        if not isinstance(t, torch.Tensor) or t.shape != (nbins, n) or t.dtype != dt or t.device != dev \
+                or not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError(f"{what}: {name} must be a contiguous, 16-B aligned {dt} [{nbins}, {n}] tensor on {dev}")
+    C = _ext.load()
+    s = _ext.stream_handle(stream)
+    for a, b in _chunks(F):
+        C.cube([_ptr(t) for t in frames[a:b]], n, lo, hi, S, nbins, blist[a:b], _ptr(nfr), _ptr(cnt), _ptr(sum),
+               _ptr(sq), s)
 
 
 def pixel_hist_tile_pixels(nbins: int) -> int:

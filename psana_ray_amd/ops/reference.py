@@ -453,6 +453,76 @@ def powder_accumulate_reference(frames: torch.Tensor, vmin: float, vmax: float, 
             torch.stack(qmax).to(torch.int32), torch.stack(above).to(torch.int32))
 
 
+# K-15 cube: K-11's window, quantisation and run bound (validate_powder_params), per bin of a scan variable
+# (docs/ARCHITECTURE.md, "Cube: the integer contract")
+CUBE_MAX_BINS = 4096
+CUBE_DROPPED = -1                # the bin of a frame that is not accumulated
+CUBE_BYTES_PER_PIXEL = 20        # cnt int32 + sum int64 + sq int64 of one bin
+
+
+def validate_cube_nbins(nbins, what: str = "cube_accumulate") -> int:
+    try:
+        nbins = operator.index(nbins)
+    except TypeError:
+        raise ValueError(f"{what}: nbins must be an integer, got {nbins!r}") from None
+    if not 1 <= nbins <= CUBE_MAX_BINS:
+        raise ValueError(f"{what}: nbins must be in [1, {CUBE_MAX_BINS}], got {nbins}")
+    return nbins
+
+
+def validate_cube_bins(bins, frames: int, nbins: int, what: str = "cube_accumulate") -> List[int]:
+    """``bins`` (a sequence, numpy array or CPU tensor of ``frames`` integers in -1 .. nbins - 1) as a list
+    of Python ints -- or ValueError."""
+    if isinstance(bins, torch.Tensor):
+        if bins.device.type != "cpu":
+            raise ValueError(f"{what}: bins live on the host, got a tensor on {bins.device}")
+        bins = bins.numpy()
+    try:
+        b = np.asarray(bins)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: bins must be integers") from None
+    if b.ndim != 1 or b.shape[0] != frames:
+        raise ValueError(f"{what}: {b.size if b.ndim == 1 else b.shape} bins for {frames} frames")
+    if frames and b.dtype.kind not in "iu":
+        raise ValueError(f"{what}: bins must be integers, got {b.dtype}")
+    out = [int(v) for v in b]
+    if any(not CUBE_DROPPED <= v < nbins for v in out):
+        raise ValueError(f"{what}: bins must be in -1 .. {nbins - 1}")
+    return out
+
+
+def cube_accumulate_reference(frames: torch.Tensor, bins, nbins: int, vmin: float, vmax: float, frac_bits: int):
+    """K-15 golden: per-pixel, per-bin statistics by exact INTEGER accumulation.  ``frames``: [F, ...]
+    float32 (any frame layout of n elements); ``bins``: F integers, frame f belongs to bin bins[f] in 0 ..
+    nbins - 1 or is dropped with -1.  A sample v of a kept frame contributes iff vmin <= v <= vmax as
+    float32 (NaN fails, +-inf is outside); it gives q = int64(round_half_even(v * 2^S)) and adds 1 to
+    cnt[b, p], q to sum[b, p] and q * q to sq[b, p].  Returns the increments (nfr int64 [B], cnt int32
+    [B, n], sum int64 [B, n], sq int64 [B, n]) of these frames alone."""
+    lo, hi, S, _thr, _Q, max_frames = validate_powder_params(vmin, vmax, frac_bits, 0.0, "cube")
+    B = validate_cube_nbins(nbins, "cube")
+    if frames.dtype != torch.float32:
+        raise ValueError(f"cube: frames must be float32, got {frames.dtype}")
+    F = int(frames.shape[0])
+    if F < 1:
+        raise ValueError("cube: no frames")
+    if F > max_frames:
+        raise ValueError(f"cube: {F} frames are more than the {max_frames} a run holds at these parameters")
+    x = frames.detach().cpu().reshape(F, -1)
+    n = x.shape[1]
+    if not 1 <= n < 2 ** 31:
+        raise ValueError("cube: frames must have 1 .. 2^31 - 1 elements")
+    b = torch.tensor(validate_cube_bins(bins, F, B, "cube"), dtype=torch.int64)
+    kept = b >= 0
+    row = b.clamp(min=0)   # a dropped frame adds zeros to bin 0
+    ok = (x >= lo) & (x <= hi) & kept.unsqueeze(1)
+    q = torch.where(ok, torch.round(x * float(2 ** S)), torch.zeros_like(x)).to(torch.int64)
+    nfr = torch.zeros(B, dtype=torch.int64).index_add_(0, row, kept.to(torch.int64))
+    cnt = torch.zeros((B, n), dtype=torch.int64).index_add_(0, row, ok.to(torch.int64))
+    s = torch.zeros((B, n), dtype=torch.int64).index_add_(0, row, q)
+    sq = torch.zeros((B, n), dtype=torch.int64).index_add_(0, row, q * q)
+    return nfr, cnt.to(torch.int32), s, sq
+
+
 # K-12 per-pixel histograms: the defaults of the contract (docs/ARCHITECTURE.md, "Pixel histograms: the
 # integer contract").  The default window is 128 wide with 64 bins: bins of exactly 2.0, inv_w exactly 0.5.
 HIST_LO = -32.0

@@ -19,7 +19,8 @@ of the frames the peak finder calls hits; PowderConsumer keeps the exact per-pix
 maximum of the calibrated frames (K-11), split into misses and hits by the same device-side filter;
 PixelHistConsumer keeps the exact per-pixel spectrum of the calibrated frames (K-12); PhotonConsumer counts
 photons per pixel with psana's neighbour merge (K-13): run maps and the per-frame P(k) of up to 8 ROIs;
-DropletConsumer writes every frame's connected clusters of pixels above a threshold as integer rows (K-14).
+DropletConsumer writes every frame's connected clusters of pixels above a threshold as integer rows (K-14);
+CubeConsumer keeps the exact per-pixel run sums of the calibrated frames per bin of a per-event scalar (K-15).
 """
 from __future__ import annotations
 
@@ -1747,3 +1748,173 @@ class DropletConsumer(_BatchConsumer):
             self._advance(keep=0)   # first pass issues the last data copies, second collects them
             self.sync_streams()
         return self.results
+
+
+class CubeConsumer(_BatchConsumer):
+    """Consumer engine: batches of leased slots -> K-15 cube (csrc/cube.hip) -> stream-ordered release.
+
+    Per run and BIN of a per-event scalar (``binning``: :class:`psana_ray_amd.cube.CubeBinning`, from the
+    photon energy or from the global event number): per-pixel count / sum / sum of squares of the quantised
+    calibrated value inside ``[vmin, vmax]`` -- integers, so the result is exact in any frame order.  A
+    frame's bin is computed on the HOST from its slot header before the launch; a frame without a bin is
+    dropped (not read).  The kernel owns a pixel per launch and uses no atomics, so every consumer stream
+    has its OWN accumulator set; :meth:`synchronize` adds the sets on the device and copies one result to
+    the host.  When the sets of all streams do not fit ``acc_budget`` bytes (default: half of the free HBM)
+    the consumer runs on one stream."""
+
+    name = "cube"
+    wants_meta = True
+
+    def __init__(self, endpoint: QueueEndpoint, frame_shape, binning, vmin: Optional[float] = None,
+                 vmax: Optional[float] = None, frac_bits: Optional[int] = None, detector: str = "",
+                 layout: str = "calib", batch: Optional[int] = None, stream_kind: str = CONSUMER_STREAM_KIND,
+                 streams: int = CONSUMER_STREAMS, ranks_per_gpu: Optional[int] = None, check_ring: bool = True,
+                 acc_budget: Optional[int] = None):
+        """frame_shape: the shape of a (calibrated) frame.  check_ring=False: the queue carries RAW
+        frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
+        from . import cube as _cube
+        from .ops import reference as _ref
+
+        self.shape = tuple(int(s) for s in frame_shape)
+        self.n = int(np.prod(self.shape))
+        if not 1 <= self.n < 2 ** 31:
+            raise ValueError("cube: frames must have 1 .. 2^31 - 1 elements")
+        self.vmin, self.vmax, self.frac_bits, _thr, _Q, self.max_frames = _ref.validate_powder_params(
+            _ref.POWDER_VMIN if vmin is None else vmin, _ref.POWDER_VMAX if vmax is None else vmax,
+            _ref.POWDER_FRAC_BITS if frac_bits is None else frac_bits, 0.0, "cube")
+        if not isinstance(binning, _cube.CubeBinning):
+            raise ValueError("cube: binning must be a psana_ray_amd.cube.CubeBinning")
+        self.binning = binning
+        self.nbins = binning.nbins
+        self.detector, self.layout = str(detector), str(layout)
+        if check_ring:
+            if endpoint.ring.dtype != torch.float32:
+                raise ValueError(f"cube: the queue carries {endpoint.ring.dtype} frames, the cube needs calibrated "
+                                 "float32 ones")
+            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
+                raise ValueError(f"cube: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+        self.set_bytes = _cube.accumulator_set_bytes(self.nbins, self.n)
+        dev = endpoint.ring.device
+        if dev.type == "cuda":
+            if acc_budget is None:
+                acc_budget = torch.cuda.mem_get_info(dev)[0] // 2   # half of the free HBM
+            fit = _cube.accumulator_sets_that_fit(self.set_bytes, streams, acc_budget)   # ValueError: not even one
+            if fit < int(streams):
+                log.info("cube: %d accumulator sets of %d bytes do not fit %d bytes: running on one stream",
+                         int(streams), self.set_bytes, acc_budget)
+            streams = fit
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        log.info("cube: %d bins x %d pixels x 20 B = %d bytes per accumulator set, %d set(s), max_frames=%d",
+                 self.nbins, self.n, self.set_bytes, max(1, len(self.streams)), self.max_frames)
+        self.dropped = 0
+        self.rows = []            # per batch: ([(rank, idx, gevt, photon_energy), ...], bins int32 [n])
+        self._bins = None         # the bins of the batch being launched
+        self._pending = None      # the meta of the batch process_frames hands to _launch_tensors
+        self._host = self._new_host()
+        if self.gpu:
+            B, n = self.nbins, self.n
+            # one accumulator set per stream; set k is only ever touched by launches on stream k
+            self._acc = [(torch.zeros(B, dtype=torch.int64, device=dev),
+                          torch.zeros((B, n), dtype=torch.int32, device=dev),
+                          torch.zeros((B, n), dtype=torch.int64, device=dev),
+                          torch.zeros((B, n), dtype=torch.int64, device=dev)) for _ in self.streams]
+
+    def _new_host(self) -> dict:
+        B, n = self.nbins, self.n
+        return {"frames": np.zeros(B, np.int64), "cnt": np.zeros((B, n), np.int32),
+                "sum": np.zeros((B, n), np.int64), "sq": np.zeros((B, n), np.int64)}
+
+    def _check_bound(self, n: int):
+        if self.frames + n > self.max_frames:
+            raise ValueError(f"cube: {self.frames} + {n} frames would take the run past max_frames = "
+                             f"{self.max_frames} (the int32 count and the int64 sum of squares)")
+
+    def _check_batch(self, n):
+        if n > self.batch:
+            raise ValueError(f"cube: {n} frames in a batch of at most {self.batch}")
+        self._check_bound(n)
+
+    def _limit(self, n_max):
+        self._check_bound(1)   # before any lease
+        return max(1, min(n_max, self.max_frames - self.frames))
+
+    def process_frames(self, frames, meta):
+        """Accumulate ``frames`` (tensors of n elements on this consumer's device, issued on the current
+        stream) that are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank, idx,
+        gevt, photon_energy)``.  GPU: returns the consumer stream the batch runs on."""
+        self._pending = [tuple(m) + (None,) * (4 - len(m)) for m in meta]
+        return super().process_frames(frames, self._pending)
+
+    def _meta_of(self, recs):
+        # a slot header carries NaN for "no photon energy", a queue item None
+        return [(r.rank, r.idx, r.gevt, None if r.photon_energy != r.photon_energy else r.photon_energy)
+                for r in recs]
+
+    def _launch_slots(self, C, slots, b, k, st):
+        # the bins come from the slot headers (a host read), before the native call
+        self._bins = self.binning.bin_of_meta(self._meta_of(self.ep.pool.headers(slots)))
+        nfr, cnt, s, q = self._acc[k]
+        C.cube_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.vmin, self.vmax, self.frac_bits,
+                     self.nbins, self._bins.tolist(), int(nfr.data_ptr()), int(cnt.data_ptr()), int(s.data_ptr()),
+                     int(q.data_ptr()), int(st.cuda_stream))
+
+    def _launch_tensors(self, frames, b, k, st):
+        self._bins = self.binning.bin_of_meta(self._pending)
+        nfr, cnt, s, q = self._acc[k]
+        kernels.cube_accumulate([t.reshape(-1) for t in frames], self._bins, self.nbins, self.vmin, self.vmax,
+                                self.frac_bits, nfr, cnt, s, q, frames_so_far=self.frames, stream=st)
+
+    def _keep_rows(self, meta, bins):
+        self.dropped += int((bins < 0).sum())
+        self.rows.append((list(meta), bins))
+
+    def _launched(self, b, n, st, meta):
+        self._keep_rows(meta, self._bins)
+
+    def _reference(self, frames, meta):
+        from .ops import reference
+
+        bins = self.binning.bin_of_meta(meta)
+        x = torch.stack([t.reshape(-1) for t in frames])
+        nfr, cnt, s, sq = reference.cube_accumulate_reference(x, bins, self.nbins, self.vmin, self.vmax,
+                                                              self.frac_bits)
+        h = self._host
+        h["frames"] += nfr.numpy()
+        h["cnt"] += cnt.numpy()
+        h["sum"] += s.numpy()
+        h["sq"] += sq.numpy()
+        self._keep_rows(meta, bins)
+
+    def synchronize(self) -> dict:
+        """Wait for every batch, add the per-stream accumulator sets ON THE DEVICE (exact: a count of the run
+        is at most its frames, which the bound keeps inside an int32) and copy the one result to the host.
+        Returns the dict of ``frames`` int64 [B], ``cnt`` int32 / ``sum`` int64 / ``sq`` int64 [B, n]."""
+        if self.gpu:
+            self.sync_streams()
+            with torch.cuda.device(self.device):
+                host = {}
+                for i, name in enumerate(("frames", "cnt", "sum", "sq")):
+                    total = self._acc[0][i]
+                    if len(self._acc) > 1:
+                        total = total.clone()
+                        for acc in self._acc[1:]:
+                            total += acc[i]
+                    host[name] = total.cpu().numpy()
+                    del total
+                self._host = host
+        return self._host
+
+    def stats(self):
+        """The (synchronised) run as a :class:`psana_ray_amd.cube.CubeStats`."""
+        from .cube import CubeStats
+
+        h = self.synchronize()
+        meta = [m for ms, _ in self.rows for m in ms]
+        bins = np.concatenate([b for _, b in self.rows]) if self.rows else np.zeros(0, np.int32)
+        bg = self.binning
+        return CubeStats(self.detector, self.layout, self.shape, self.vmin, self.vmax, self.frac_bits, bg.by,
+                         self.nbins, bg.edges, bg.table_sha256, h["frames"].copy(), self.dropped, h["cnt"].copy(),
+                         h["sum"].copy(), h["sq"].copy(), rank=[m[0] for m in meta], idx=[m[1] for m in meta],
+                         gevt=[m[2] for m in meta],
+                         photon_energy=[float("nan") if m[3] is None else float(m[3]) for m in meta],
+                         bin=bins.astype(np.int16))

@@ -77,7 +77,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--data_dir", type=str, default=None, help="raw-run files directory (or $PSANA_RAY_DATA)")
     g.add_argument("--chunk", type=int, default=64, help="frames per H2D copy / kernel launch (<= 64)")
     g.add_argument("--route", type=str, default="balanced", choices=["balanced", "local_first", "spread"])
-    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets"],
+    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets", "cube"],
                    help="also consume on every producer rank (co-located consumer, BASELINE config 5): the K-07 "
                         "peak finder, the K-08 radial profile (default binning of psana-ray-consumer), the K-09 "
                         "dark statistics (needs --mode raw; --out_dark writes the file), or the K-10 zero "
@@ -88,7 +88,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "psana-ray-consumer --task hist), or the K-13 photon counting (--out_photons writes the file; "
                         "--adu_per_photon ... --photon_roi as for psana-ray-consumer --task photons), or the K-14 "
                         "droplets (--out_droplets writes the file; --drop_thr_low ... --drop_mask as for "
-                        "psana-ray-consumer --task droplets)")
+                        "psana-ray-consumer --task droplets), or the K-15 cube (--out_cube writes the file; "
+                        "--cube_by ... --cube_frac_bits as for psana-ray-consumer --task cube)")
+    g.add_argument("--out_cube", type=str, default=None,
+                   help="--consumer_task cube: write the rank's cube (psana_ray_amd.cube.CubeStats .npz) here")
     g.add_argument("--out_droplets", type=str, default=None,
                    help="--consumer_task droplets: write the rank's droplet lists "
                         "(psana_ray_amd.droplets.DropletFrames .npz) here")
@@ -132,14 +135,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "the SDMA engines (utils/runtime_env.py)")
     g.add_argument("--local", action="store_true",
                    help="single-process queue: no rendezvous; requires --consumer_task (no external consumers)")
-    from .consumer import (add_droplet_arguments, add_hist_arguments, add_photon_arguments, add_powder_arguments,
-                           add_sparse_arguments)
+    from .consumer import (add_cube_arguments, add_droplet_arguments, add_hist_arguments, add_photon_arguments,
+                           add_powder_arguments, add_sparse_arguments)
 
     add_sparse_arguments(parser)
     add_powder_arguments(parser)
     add_hist_arguments(parser)
     add_photon_arguments(parser)
     add_droplet_arguments(parser)
+    add_cube_arguments(parser)
     return parser
 
 
@@ -303,7 +307,7 @@ def main(argv=None) -> int:
                       "or a co-located --consumer_task")
             return 2
         mode = Mode.raw   # frames travel raw; DataReader applies read_mode
-    if args.consumer_task in ("radial", "sparse", "powder", "hist", "photons", "droplets") and (mode == Mode.raw or int(args.panel_shards) > 1):
+    if args.consumer_task in ("radial", "sparse", "powder", "hist", "photons", "droplets", "cube") and (mode == Mode.raw or int(args.panel_shards) > 1):
         log.error("--consumer_task %s needs whole calibrated frames (not --mode raw / --panel_shards)",
                   args.consumer_task)
         return 2
@@ -311,13 +315,21 @@ def main(argv=None) -> int:
         log.error("--consumer_task dark needs whole raw frames (--mode raw, no --panel_shards)")
         return 2
     for flag, task in (("out_sparse", "sparse"), ("out_dark", "dark"), ("out_powder", "powder"),
-                       ("out_hist", "hist"), ("out_photons", "photons"), ("out_droplets", "droplets")):
+                       ("out_hist", "hist"), ("out_photons", "photons"), ("out_droplets", "droplets"), ("out_cube", "cube")):
         if getattr(args, flag) is not None and args.consumer_task != task:
             log.error("--%s belongs to --consumer_task %s", flag, task)
             return 2
     if args.consumer_task == "photons" and args.adu_per_photon is None:
         log.error("--consumer_task photons needs --adu_per_photon")
         return 2
+    if args.consumer_task == "cube":   # the bin source is checked before anything starts
+        from .consumer import cube_binning
+
+        try:
+            cube_binning(args)
+        except (ValueError, OSError) as e:
+            log.error("--consumer_task cube: %s", e)
+            return 2
     if args.consumer_task == "droplets" and args.drop_thr_low is None:
         log.error("--consumer_task droplets needs --drop_thr_low")
         return 2
@@ -442,7 +454,7 @@ def main(argv=None) -> int:
             # consumer thread, at the end of the stream), report(result or None, frames consumed) after the join
             each = None
 
-            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder / .hist / .photons / .droplets merge)
+            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder / .hist / .photons / .droplets / .cube merge)
                 root, ext = os.path.splitext(path)
                 return path if size == 1 else f"{root}.r{rank}{ext}"
 
@@ -576,6 +588,25 @@ def main(argv=None) -> int:
                         path = rank_path(args.out_droplets)
                         df.save(path)
                         log.info("Rank %d: droplet lists written to %s", rank, path)
+            elif args.consumer_task == "cube":
+                try:
+                    from .consumer import cube_binning, cube_final_line, cube_start_line
+                    from .pipeline import CubeConsumer
+
+                    cons = CubeConsumer(ep, frame_shape, cube_binning(args), vmin=args.cube_vmin, vmax=args.cube_vmax,
+                                        frac_bits=args.cube_frac_bits, detector=args.detector_name, layout=mode.value)
+                except (ValueError, OSError) as e:
+                    log.error("--consumer_task cube: %s", e)
+                    return 2
+                print(cube_start_line(rank, cons), flush=True)
+                finish = cons.stats
+
+                def report(cs, consumed):
+                    print(cube_final_line(rank, cs, consumed), flush=True)
+                    if cs is not None and args.out_cube:
+                        path = rank_path(args.out_cube)
+                        cs.save(path)
+                        log.info("Rank %d: cube written to %s", rank, path)
             else:
                 cons = PeakFinderConsumer(ep, frame_shape, PeakFinderParams())
                 finish = cons.synchronize
