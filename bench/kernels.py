@@ -628,6 +628,95 @@ def main(argv=None):
                     "vs_powder": round(mc[0] / mp[0], 3), "time_vs_G1": round(mc[0] / m1[0], 3),
                     "bytes_vs_G1": round(nbytes / (fbytes + 40 * npix), 3),
                     "TB_per_s": round(nbytes / mc[0] / 1e12, 3)}, frames=FR)
+    if want("roi"):
+        # K-16 ROI statistics: 64 SEPARATELY allocated calib frames, four sets of rectangles, alternating in the
+        # same process with the read floor, powder(NC=1) on the SAME frames and the smallest launch there is (one
+        # pixel: the clear and a grid of 64 workgroups) -- the median round of each.  Bytes: 4 B per pixel of the
+        # rectangles and frame, plus the rows (64 B per rectangle and frame) and the projection words.
+        from psana_ray_amd.ops.reference import (POWDER_FRAC_BITS, POWDER_QMAX_NONE, POWDER_THR_ABOVE, POWDER_VMAX,
+                                                 POWDER_VMIN, ROI_FRAC_BITS, ROI_VMAX, ROI_VMIN)
+
+        FR, rounds = 64, 5
+        C = _ext.load()
+        P, H, W = spec.frame_shape
+        rraw = [pool[i % pool.shape[0]].to(dev).clone() for i in range(FR)]
+        rfl = [torch.empty(spec.frame_shape, dtype=torch.float32, device=dev) for _ in range(FR)]
+        cal.run(rraw, rfl)
+        torch.cuda.synchronize()
+        del rraw
+        rflat = [t.reshape(-1) for t in rfl]
+        fp64 = [int(t.data_ptr()) for t in rfl]
+        sums = torch.zeros(FR, dtype=torch.float32, device=dev)
+        pacc = (torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros((1, npix), dtype=torch.int32, device=dev),
+                torch.zeros((1, npix), dtype=torch.int64, device=dev), torch.zeros((1, npix), dtype=torch.int64, device=dev),
+                torch.full((1, npix), POWDER_QMAX_NONE, dtype=torch.int32, device=dev),
+                torch.zeros((1, npix), dtype=torch.int32, device=dev))
+        panels = [(p, 0, H, 0, W) for p in range(min(P, 16))]
+        sh, sw, th = min(64, H), min(384, W), min(352, H)
+        cases = (("a: whole panels", panels, "none"), ("b: whole panels, both projections", panels, "both"),
+                 (f"c: one {sh}x{sw} stripe, proj x", [(P // 2, (H - sh) // 2, (H - sh) // 2 + sh, 0, sw)], "x"),
+                 (f"d: one {th}x16 stripe, proj y", [(P // 2, 0, th, 16, 32)], "y"),
+                 ("empty: one pixel", [(0, 0, 1, 0, 1)], "none"))
+
+        def bufs(rects, proj):
+            Lx = sum(r[4] - r[3] for r in rects) if proj in ("x", "both") else 0
+            Ly = sum(r[2] - r[1] for r in rects) if proj in ("y", "both") else 0
+            return (torch.zeros((FR, len(rects), 8), dtype=torch.int64, device=dev),
+                    torch.zeros((FR, Lx), dtype=torch.int64, device=dev) if Lx else None,
+                    torch.zeros((FR, Ly), dtype=torch.int64, device=dev) if Ly else None)
+
+        rb = [bufs(r, p) for _, r, p in cases]
+        strip0, ahead0 = C.roi_strip_pixels(), C.roi_rows_ahead()
+        # the shipped launch shape, then (measurements only) two larger strip sizes, and 1 and 2 row iterations'
+        # loads in flight forced (shipped: 2 for grids of up to 2048 workgroups, 1 beyond)
+        strips = (strip0, 2 * strip0, 4 * strip0, -1, -2)
+
+        def rf(k, sp):
+            _, rects, _proj = cases[k]
+            rows, px, py = rb[k]
+
+            def fn():
+                kernels.roi_stats(rflat, spec.frame_shape, rects, ROI_VMIN, ROI_VMAX, ROI_FRAC_BITS, rows, px, py)
+            C.roi_strip_pixels(sp if sp > 0 else strip0)   # the plan is built (and cached per strip size) here
+            C.roi_rows_ahead(-sp if sp < 0 else ahead0)        # read at launch (and so at graph capture)
+            fn()
+            return fn
+
+        t_read, t_pow, t_roi = [], [], {(k, sp): [] for k in range(len(cases)) for sp in strips}
+        for _ in range(rounds):
+            t_read.append(timeit(lambda: C.read_f32(fp64, npix, 16, False, int(sums.data_ptr()), _ext.stream_handle()),
+                                 a.iters))
+            for t, v in zip(pacc, (0, 0, 0, 0, POWDER_QMAX_NONE, 0)):
+                t.fill_(v)
+            t_pow.append(timeit(lambda: kernels.powder_accumulate(rflat, POWDER_VMIN, POWDER_VMAX, POWDER_FRAC_BITS,
+                                                                  POWDER_THR_ABOVE, *pacc), a.iters))
+            for k in range(len(cases)):
+                for sp in strips:
+                    t_roi[k, sp].append(timeit(rf(k, sp), a.iters))
+        C.roi_strip_pixels(strip0)
+        C.roi_rows_ahead(ahead0)
+        med = lambda ts: sorted(ts)[rounds // 2]   # noqa: E731
+        us = lambda ts: [round(t[0] * 1e6 / FR, 3) for t in ts]   # noqa: E731
+        mr, mp = med(t_read), med(t_pow)
+        fbytes = FR * npix * 4
+        report("read_f32 reference (K=16)", mr, fbytes, {"rounds_us_per_frame": us(t_read)}, frames=FR)
+        report("powder(NC=1)", mp, fbytes + npix * 56,
+               {"rounds_us_per_frame": us(t_pow), "vs_read_floor": round(mp[0] / mr[0], 3)}, frames=FR)
+        me = med(t_roi[len(cases) - 1, strip0])
+        for sp in strips:
+            for k, (name, rects, proj) in enumerate(cases):
+                mc = med(t_roi[k, sp])
+                area = sum((r[2] - r[1]) * (r[4] - r[3]) for r in rects)
+                out_b = sum(0 if t is None else t.numel() * 8 for t in rb[k])
+                nbytes = FR * area * 4 + out_b
+                report(f"roi({name})" + ("" if sp == strip0 else f" [strips of {sp} px]" if sp > 0 else
+                                        f" [{-sp} row iteration(s) of loads in flight]"), mc, nbytes,
+                       {"rois": len(rects), "proj": proj, "strip_pixels": sp if sp > 0 else strip0,
+                        "rows_ahead": -sp if sp < 0 else ahead0, "area_frac": round(area / npix, 5),
+                        "us_per_batch": round(mc[0] * 1e6, 2),
+                        "rounds_us_per_batch": [round(t[0] * 1e6, 2) for t in t_roi[k, sp]],
+                        "vs_read_floor": round(mc[0] / mr[0], 3), "vs_powder": round(mc[0] / mp[0], 3),
+                        "vs_empty_launch": round(mc[0] / me[0], 3)}, frames=FR)
     if want("h2d"):
         C = _ext.load()
         hp = src.pool

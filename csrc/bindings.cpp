@@ -99,7 +99,7 @@ static FramePtrs make_ptrs(const std::vector<uint64_t>& in, const std::vector<ui
 }
 
 // The consumers' ring-slot bindings (peakfind_slots, radial_slots, dark_slots, sparsify_slots,
-// powder_slots, pixel_hist_slots, photons_slots, droplets_slots, cube_slots): the two
+// powder_slots, pixel_hist_slots, photons_slots, droplets_slots, cube_slots, roi_slots): the two
 // checks they share, then fn(index of the chunk's first slot, its slot pointers) for every chunk of at
 // most kMaxFrames slots.
 template <class Fn>
@@ -556,6 +556,49 @@ PYBIND11_MODULE(_C, m) {
         py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("n"), py::arg("vmin"), py::arg("vmax"),
         py::arg("frac_bits"), py::arg("nbins"), py::arg("bins"), py::arg("nfr"), py::arg("cnt"), py::arg("sum"),
         py::arg("sq"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+
+  py::class_<pr::RoiPlan, std::shared_ptr<pr::RoiPlan>>(m, "RoiPlan",
+      "K-16: the rectangles of a run cut into strips, on the device (built once, reused by every launch)")
+      .def(py::init<const std::vector<int32_t>&, int, int, int, int>(), py::arg("rects"), py::arg("P"), py::arg("H"),
+           py::arg("W"), py::arg("device"))
+      .def_readonly("R", &pr::RoiPlan::R)
+      .def_readonly("nstrips", &pr::RoiPlan::nstrips)
+      .def_readonly("Lx", &pr::RoiPlan::Lx)
+      .def_readonly("Ly", &pr::RoiPlan::Ly)
+      .def_readonly("device", &pr::RoiPlan::device);
+  m.def("roi",
+        [](const std::vector<uint64_t>& in, const pr::RoiPlan& plan, float vmin, float vmax, int frac_bits, uint64_t mask,
+           uint64_t rows, uint64_t projx, uint64_t projy, uint64_t stream) {
+          pr::launch_roi(make_ptrs(in, in), (int)in.size(), plan, vmin, vmax, frac_bits, mask, rows, projx, projy, stream);
+        },
+        py::arg("in_ptrs"), py::arg("plan"), py::arg("vmin"), py::arg("vmax"), py::arg("frac_bits"), py::arg("mask"),
+        py::arg("rows"), py::arg("projx"), py::arg("projy"), py::arg("stream"),
+        "K-16 ROI statistics of up to 64 float32 frames: clears, then fills rows uint64 [F, R, 8] (/ projx / projy)");
+  // consumer hot path: ring slots -> per-frame ROI rows and projections, one native call
+  m.def("roi_slots",
+        [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, const pr::RoiPlan& plan, float vmin,
+           float vmax, int frac_bits, uint64_t mask, uint64_t rows, uint64_t projx, uint64_t projy, uint64_t stream) {
+          for_slot_chunks(pool, slot_bytes, slots, (int64_t)plan.P * plan.H * plan.W * 4, "roi_slots",
+                          [&](int a, const std::vector<uint64_t>& in) {
+                            pr::launch_roi(make_ptrs(in, in), (int)in.size(), plan, vmin, vmax, frac_bits, mask,
+                                           rows + (uint64_t)a * plan.R * 64,
+                                           projx == 0 ? 0 : projx + (uint64_t)a * plan.Lx * 8,
+                                           projy == 0 ? 0 : projy + (uint64_t)a * plan.Ly * 8, stream);
+                          });
+        },
+        py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("plan"), py::arg("vmin"), py::arg("vmax"),
+        py::arg("frac_bits"), py::arg("mask"), py::arg("rows"), py::arg("projx"), py::arg("projy"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("roi_strip_rows", &pr::roi_strip_rows, py::arg("width"),
+        "rows of one strip (one workgroup) of a K-16 rectangle of this width");
+  m.def("roi_rows_ahead", &pr::roi_rows_ahead, py::arg("set") = -1,
+        "tests and measurements only: force the row iterations of the K-16 kernel whose loads are in flight together "
+        "(1 or 2; 0 = by the grid's size, the default); -1 = only return the setting");
+  m.def("roi_strip_pixels", &pr::roi_strip_pixels, py::arg("set") = 0,
+        "measurements only: the pixels of a strip (about) of the K-16 plans built from now on; 0 = only return it");
+  m.def("roi_plan_strips", &pr::roi_plan_strips, py::arg("rects"), py::arg("P"), py::arg("H"), py::arg("W"),
+        "the strips of a K-16 plan, 8 int32 words each: r, p * H + y, rows, x0, x1, y, offx, offy + dy");
+  m.attr("ROI_MAX_RECTS") = pr::kRoiMaxRects;
 
   m.def("copy_h2d_kernel",
         [](uint64_t dst, uint64_t src, int64_t bytes, int workgroups, uint64_t stream) {

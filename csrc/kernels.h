@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "common.h"
 
 namespace pr {
@@ -144,4 +146,33 @@ void launch_droplets(const FramePtrs& fp, int nframes, int P, int H, int W, floa
 constexpr int kCubeMaxBins = 4096;
 void launch_cube(const FramePtrs& fp, int nframes, int64_t n, float vmin, float vmax, int frac_bits, int nbins,
                  const int32_t* bins, uint64_t nfr, uint64_t cnt, uint64_t sum, uint64_t sq, uint64_t stream);
+// K-16 ROI statistics (csrc/roi.hip): per frame and rectangle of up to kMaxFrames float32 frames of shape
+// [P, H, W] the row of eight 64-bit words npix, sum q, sum q * y, sum q * x, key, 0, 0, 0 over the pixels
+// with vmin <= v <= vmax that the mask (uint8 [n], 0 = all kept) keeps, q = rintf(v * 2^frac_bits); key packs
+// the largest q and the lowest index that attains it (0 = no sample).  rows: uint64 [F, R, 8], 64-B aligned;
+// projx int64 [F, Lx] / projy int64 [F, Ly] (0 = not wanted): the rectangles' column / row sums, one after
+// the other.  Clears all three for its F frames on the stream first, and touches nothing beyond them.
+// RoiPlan: the rectangles (p, y0, y1, x0, x1; half-open, at most kRoiMaxRects, overlaps allowed) cut into
+// strips of roi_strip_rows(width) rows, one per workgroup; built once per run, it owns its device copy.
+constexpr int kRoiMaxRects = 16;
+int roi_strip_rows(int width);
+// tests and measurements only: force 1 or 2 row iterations' loads in flight (0 = by the grid's size, the default;
+// -1 = only return the setting)
+int roi_rows_ahead(int set = -1);
+int roi_strip_pixels(int set = 0);   // measurements only: another strip size for the plans built from now on; returns it
+// the strips of a plan as the kernel reads them, 8 int32 words each: r, p * H + y, rows, x0, x1, y, offx, offy + dy
+std::vector<int32_t> roi_plan_strips(const std::vector<int32_t>& rects, int P, int H, int W);
+struct RoiPlan {
+  RoiPlan(const std::vector<int32_t>& rects, int P, int H, int W, int device);
+  ~RoiPlan();
+  RoiPlan(const RoiPlan&) = delete;
+  RoiPlan& operator=(const RoiPlan&) = delete;
+  int P, H, W, device;
+  int R = 0, nstrips = 0;
+  int64_t Lx = 0, Ly = 0;
+  std::vector<int32_t> rects;
+  uint64_t strips = 0;   // RoiStrip [nstrips] on the device
+};
+void launch_roi(const FramePtrs& fp, int nframes, const RoiPlan& plan, float vmin, float vmax, int frac_bits,
+                uint64_t mask, uint64_t rows, uint64_t projx, uint64_t projy, uint64_t stream);
 }  // namespace pr

@@ -18,12 +18,14 @@ calibrated frames, for gain maps), ``photons`` (on-GPU K-13 photon counting: pho
 neighbour merge, run maps and the per-frame P(k) of up to 8 ROIs), ``droplets`` (on-GPU K-14 connected-pixel
 clusters of every frame: label, pixel count, summed charge and centre of mass as integers), ``cube`` (on-GPU
 K-15 cube: exact per-pixel run sums of the calibrated frames per bin of the photon energy or of a per-event
-table) or ``none``.  ``--out`` writes the peak lists / the radial accumulator / the dark
+table), ``roi`` (on-GPU K-16 ROI statistics: per frame the sum, centre of mass, maximum and projections of up to
+16 rectangles, read from the rectangles alone) or ``none``.  ``--out`` writes the peak lists / the radial accumulator / the dark
 statistics / the sparse frames / the powder statistics to an ``.npz`` (several consumers' radial files add
 with ``psana_ray_amd.radial.merge``, dark files with ``psana_ray_amd.dark.merge``, sparse files join with
 ``psana_ray_amd.sparse.merge``, powder files merge with ``psana_ray_amd.powder.merge``, histogram files with
 ``psana_ray_amd.hist.merge``, photon files with ``psana_ray_amd.photons.merge``, droplet files with
-``psana_ray_amd.droplets.merge``, cube files with ``psana_ray_amd.cube.merge``).
+``psana_ray_amd.droplets.merge``, cube files with ``psana_ray_amd.cube.merge``, ROI files with
+``psana_ray_amd.roi.merge``).
 """
 from __future__ import annotations
 
@@ -48,7 +50,7 @@ def build_parser():
     ap.add_argument("--ray_namespace", type=str, default=DEFAULT_RAY_NAMESPACE)
     ap.add_argument("--queue_name", type=str, default=DEFAULT_QUEUE_NAME)
     ap.add_argument("--device", type=str, default=None)
-    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets", "cube", "train", "none"],
+    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets", "cube", "roi", "train", "none"],
                     help="train: online PeakNetLite training from peak-finder labels (trainer.py); radial: radial "
                          "profile I(r) / I(q) of every frame + run accumulator (--nbins ... --radial_mask); dark: "
                          "per-pixel dark-run statistics of a RAW queue (--adu_min / --adu_max); sparse: zero-suppressed "
@@ -57,7 +59,8 @@ def build_parser():
                          "histograms of the calibrated frames (--hist_lo --hist_hi --hist_bins); photons: photons per pixel "
                          "of the calibrated frames (--adu_per_photon ... --photon_roi); droplets: connected clusters of "
                          "pixels above a threshold per frame (--drop_thr_low ... --drop_mask); cube: per-pixel run sums "
-                         "per bin of the photon energy or of a per-event table (--cube_by ... --cube_frac_bits)")
+                         "per bin of the photon energy or of a per-event table (--cube_by ... --cube_frac_bits); roi: per frame "
+                         "the sum, centre of mass, maximum and projections of up to 16 rectangles (--roi ... --roi_mask)")
     ap.add_argument("--lr", type=float, default=1e-3, help="--task train: AdamW learning rate")
     ap.add_argument("--save", type=str, default=None, help="--task train: write the model state_dict here")
     ap.add_argument("--ddp", action="store_true",
@@ -80,7 +83,8 @@ def build_parser():
                          "(psana_ray_amd.hist.PixelHist npz) when --task hist; the photon statistics "
                          "(psana_ray_amd.photons.PhotonStats npz) when --task photons; the droplet lists "
                          "(psana_ray_amd.droplets.DropletFrames npz) when --task droplets; the cube "
-                         "(psana_ray_amd.cube.CubeStats npz) when --task cube")
+                         "(psana_ray_amd.cube.CubeStats npz) when --task cube; the per-frame ROI records "
+                         "(psana_ray_amd.roi.RoiFrames npz) when --task roi")
     g = ap.add_argument_group("--task radial")
     g.add_argument("--nbins", type=int, default=512, help="radial bins (1 .. 4096)")
     g.add_argument("--center", type=str, default=None, help="beam centre Y,X in image pixels (default: image centre)")
@@ -104,6 +108,7 @@ def build_parser():
     add_photon_arguments(ap)
     add_droplet_arguments(ap)
     add_cube_arguments(ap)
+    add_roi_arguments(ap)
     ap.add_argument("--timeout", type=float, default=300.0)
     ap.add_argument("--metrics_interval", type=float, default=10.0, help="seconds between rate lines; 0 disables")
     ap.add_argument("--metrics_json", type=str, default=None, help="append per-interval metrics as JSON lines")
@@ -216,6 +221,79 @@ def add_cube_arguments(ap):
     g.add_argument("--cube_frac_bits", type=int, default=2,
                    help="values are accumulated as round(v * 2^S), S in 0 .. 16 (default 2); max(|vmin|, |vmax|) * 2^S "
                         "must stay below 2^31 and bounds the frames of a run (printed at start)")
+
+
+def add_roi_arguments(ap):
+    """The flags of ``--task roi`` (the producer CLI's ``--consumer_task roi`` takes the same)."""
+    g = ap.add_argument_group("--task roi")
+    g.add_argument("--roi", action="append", default=None, metavar="SPEC",
+                   help="a rectangle P,Y0:Y1,X0:X1 (panel, rows, columns; half-open) -- Y0:Y1,X0:X1 for 2-D (image) "
+                        "frames; repeat for up to 16 rectangles, which may overlap")
+    g.add_argument("--roi_file", type=str, default=None,
+                   help="integer .npy of [R, 5] rows (p, y0, y1, x0, x1) -- [R, 4] for 2-D frames -- instead of --roi")
+    g.add_argument("--roi_proj", type=str, default="none", choices=["none", "x", "y", "both"],
+                   help="also keep per frame every rectangle's sum over its rows per column (x), over its columns per "
+                        "row (y), or both (default none)")
+    g.add_argument("--roi_vmin", type=float, default=-float(2 ** 20),
+                   help="value window: pixels below are ignored (default -2^20)")
+    g.add_argument("--roi_vmax", type=float, default=float(2 ** 20),
+                   help="value window: pixels above are ignored (default 2^20)")
+    g.add_argument("--roi_frac_bits", type=int, default=2,
+                   help="values are summed as round(v * 2^S), S in 0 .. 16 (default 2); Q = max(|vmin|, |vmax|) * 2^S "
+                        "must stay below 2^31, and Q x area x the largest row / column index of a rectangle within "
+                        "2^63 - 1")
+    g.add_argument("--roi_mask", type=str, default=None,
+                   help=".npy keep-mask of the frames' shape: non-zero = keep (default: every pixel)")
+
+
+def roi_check_flags(args):
+    """What can be said about the ``--roi*`` flags before the frames' shape is known, or a ValueError: a source of
+    rectangles (one, not both), well-formed specs, a possible window."""
+    from .ops.reference import validate_roi_params
+    from .roi import RoiSet
+
+    if not args.roi and args.roi_file is None:
+        raise ValueError("no rectangle: --roi P,Y0:Y1,X0:X1 (repeatable) or --roi_file PATH.npy")
+    if args.roi and args.roi_file is not None:
+        raise ValueError("give --roi or --roi_file, not both")
+    for spec in args.roi or ():
+        try:
+            RoiSet.parse_spec(spec, 3)
+        except ValueError:
+            RoiSet.parse_spec(spec, 2)   # malformed for both: this one's message
+    validate_roi_params(args.roi_vmin, args.roi_vmax, args.roi_frac_bits, None, "roi")
+
+
+def roi_consumer(args, endpoint, shape, name, layout, check_ring=True, batch=None):
+    """The RoiConsumer of ``--task roi`` / ``--consumer_task roi`` from the ``--roi*`` flags (ValueError / OSError)."""
+    from .pipeline import RoiConsumer
+    from .roi import RoiSet
+
+    roi_check_flags(args)
+    shape = tuple(shape)
+    fshape = shape[1:] if layout == "image" and len(shape) == 3 and shape[0] == 1 else shape   # an image is 2-D
+    rs = RoiSet.from_file(args.roi_file, fshape) if args.roi_file is not None else RoiSet.from_specs(args.roi, fshape)
+    mask = None
+    if args.roi_mask:
+        import numpy as np
+
+        m = np.load(args.roi_mask)   # allow_pickle stays False
+        if tuple(m.shape) not in (shape, fshape):
+            raise ValueError(f"--roi_mask is {tuple(m.shape)}, the frames are {shape}")
+        mask = (m != 0).astype(np.uint8).reshape(-1)
+    return RoiConsumer(endpoint, fshape, rs, vmin=args.roi_vmin, vmax=args.roi_vmax, frac_bits=args.roi_frac_bits,
+                       proj=args.roi_proj, mask=mask, detector=name, layout=layout, batch=batch,
+                       check_ring=check_ring)
+
+
+def roi_start_line(cid, cons) -> str:
+    return (f"Consumer {cid} roi: rois={cons.n_roi} proj={cons.proj} window=[{cons.vmin:g},{cons.vmax:g}] "
+            f"frac_bits={cons.frac_bits} batch={cons.batch} row_bytes={cons.row_bytes}")
+
+
+def roi_final_line(cid, cons, name, layout) -> str:
+    return (f"Consumer {cid} roi: frames={cons.frames} rois={cons.n_roi} row_bytes={cons.row_bytes} detector={name} "
+            f"layout={layout}")
 
 
 def cube_binning(args):
@@ -808,6 +886,35 @@ def run_cube(args, reader, stop, progress) -> int:
     return rc
 
 
+def run_roi(args, reader, stop, progress) -> int:
+    """--task roi: per-frame ROI records until the end of the stream; ``progress["n"]`` counts frames."""
+    cid = reader.consumer_id
+    if not _has_whole_frames(reader, "roi", "ROI statistics"):
+        return 2
+    cal = reader.calibrator
+    try:
+        name, layout, shape = sparse_layout(reader, args, needs="ROI statistics need")
+    except ValueError as e:
+        log.error("--task roi: %s", e)
+        return 2
+    if not name:
+        log.error("--task roi: the session does not name its detector; pass --detector_name")
+        return 2
+    try:
+        cons = roi_consumer(args, reader.endpoint, shape, name, layout, check_ring=cal is None, batch=args.batch)
+    except (ValueError, KeyError, OSError) as e:
+        log.error("--task roi: %s", e)
+        return 2
+    print(roi_start_line(cid, cons), flush=True)
+    rc = _drive(args, reader, stop, progress, cons,
+                raw_meta=None if cal is None else lambda it: (it.rank, it.idx, it.gevt, it.photon_energy))
+    st = cons.stats()
+    print(roi_final_line(cid, cons, name, layout), flush=True)
+    if args.out:
+        st.save(args.out)
+    return rc
+
+
 def run_droplets(args, reader, stop, progress) -> int:
     """--task droplets: find droplets until the end of the stream; ``progress["n"]`` counts frames."""
     from . import droplets
@@ -856,6 +963,12 @@ def main(argv=None) -> int:
         except (ValueError, OSError) as e:
             print(f"psana-ray-consumer: --task cube: {e}", file=sys.stderr)
             return 2
+    if args.task == "roi":   # the rectangles are checked before the queue is joined
+        try:
+            roi_check_flags(args)
+        except (ValueError, OSError) as e:
+            print(f"psana-ray-consumer: --task roi: {e}", file=sys.stderr)
+            return 2
     logging.basicConfig(level=getattr(logging, args.log_level), format="%(asctime)s - %(levelname)s - %(message)s")
     import numpy as np
     import torch
@@ -891,7 +1004,8 @@ def main(argv=None) -> int:
                             json_path=args.metrics_json).start()
         pf = None
         run_task = {"radial": run_radial, "dark": run_dark, "sparse": run_sparse, "powder": run_powder,
-                    "hist": run_hist, "photons": run_photons, "droplets": run_droplets, "cube": run_cube}.get(args.task)
+                    "hist": run_hist, "photons": run_photons, "droplets": run_droplets, "cube": run_cube,
+                    "roi": run_roi}.get(args.task)
         if run_task is not None:   # the tasks that run a pipeline consumer to the end of the stream
             progress = {"n": 0}
             registry.register(args.task, lambda: {"frames_consumed": progress["n"]})

@@ -1,4 +1,4 @@
-"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-15).
+"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-16).
 
 Every wrapper checks device / dtype / shape / contiguity / alignment on the host BEFORE the
 launch (a mis-shaped launch of a hand-written kernel can fault the GPU), splits batches into
@@ -542,6 +542,78 @@ def photons(frames: Sequence[torch.Tensor], shape, adu_per_photon, cnt: torch.Te
         C.photons([_ptr(t) for t in frames[a:b]], P, H, W, pp.inv, pp.vmax, pp.thr_seed, pp.thr_total, pm, pr, R,
                   0 if kmap is None else _ptr(kmap[a:b]), _ptr(cnt), _ptr(psum), _ptr(occ), _ptr(pk[a:b]),
                   _ptr(tot[a:b]), s, int(_variant))
+
+
+def roi_strip_rows(width: int) -> int:
+    """The rows of one strip (one workgroup) of a K-16 rectangle ``width`` columns wide: a taller rectangle is
+    cut into several strips.  The heights around it are where the kernel changes from one workgroup to several."""
+    return int(_ext.load().roi_strip_rows(int(width)))
+
+
+_ROI_PLANS: dict = {}    # (device index, (P, H, W), the rectangles' bytes) -> the device plan
+_ROI_PLANS_MAX = 16
+
+
+def roi_plan(shape, rects, device):
+    """The device plan of K-16 (csrc/roi.hip RoiPlan) for validated int32 [R, 5] rectangles on frames of
+    ``shape`` = (P, H, W): built once per (device, shape, rectangles), then reused by every launch."""
+    import numpy as np
+
+    dev = torch.device(device)
+    idx = torch.cuda.current_device() if dev.index is None else dev.index
+    rc = np.ascontiguousarray(rects, dtype=np.int32)
+    key = (idx, tuple(int(s) for s in shape), rc.tobytes(), int(_ext.load().roi_strip_pixels()))
+    plan = _ROI_PLANS.get(key)
+    if plan is None:
+        if len(_ROI_PLANS) >= _ROI_PLANS_MAX:
+            _ROI_PLANS.pop(next(iter(_ROI_PLANS)))
+        P, H, W = key[1]
+        plan = _ROI_PLANS[key] = _ext.load().RoiPlan(rc.reshape(-1).tolist(), P, H, W, idx)
+    return plan
+
+
+def roi_stats(frames: Sequence[torch.Tensor], shape, rects, vmin, vmax, frac_bits, rows: torch.Tensor,
+              proj_x: Optional[torch.Tensor] = None, proj_y: Optional[torch.Tensor] = None,
+              mask: Optional[torch.Tensor] = None, stream=None):
+    """K-16 ROI statistics (csrc/roi.hip; contract: ops.reference.roi_stats_reference).
+    frames: F float32 tensors of ``shape`` = [P, H, W] (or [H, W]) on one GPU; ``rects``: int [R, 5] of (p, y0,
+    y1, x0, x1), half-open.  Fills ``rows`` int64 [F, R, 8] (npix, sum, sy, sx, key, 0, 0, 0) and, when given,
+    ``proj_x`` int64 [F, Lx] / ``proj_y`` int64 [F, Ly] (the rectangles' column / row sums one after the other);
+    all three are cleared by the call for its F frames.  ``mask``: uint8 [n] on the device, non-zero = keep.
+    One call is complete in itself and may run on any stream.  Everything is checked here, before any launch."""
+    from .reference import ROI_ROW_WORDS, photon_shape, roi_offsets, validate_roi_params, validate_roi_rects
+
+    what = "roi_stats"
+    P, H, W = photon_shape(shape, what)
+    n = P * H * W
+    rc = validate_roi_rects(rects, (P, H, W), what)
+    lo, hi, S, _Q = validate_roi_params(vmin, vmax, frac_bits, rc, what)
+    R = rc.shape[0]
+    offx, offy = roi_offsets(rc)
+    F = len(frames)
+    if F == 0:
+        return
+    if not isinstance(frames[0], torch.Tensor):
+        raise ValueError(f"{what}: frames must be tensors")
+    dev = frames[0].device
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: frames on {dev}, expected a GPU")
+    _check_frames(frames, torch.float32, n, dev, f"{what} in")
+    if not isinstance(rows, torch.Tensor) or tuple(rows.shape) != (F, R, ROI_ROW_WORDS) or rows.dtype != torch.int64 \
+            or rows.device != dev or not rows.is_contiguous() or rows.data_ptr() % 64:
+        raise ValueError(f"{what}: rows must be a contiguous, 64-B aligned int64 [{F}, {R}, {ROI_ROW_WORDS}] tensor "
+                         f"on {dev}")
+    for t, L, name in ((proj_x, int(offx[-1]), "proj_x"), (proj_y, int(offy[-1]), "proj_y")):
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (F, L) or t.dtype != torch.int64
+                              or t.device != dev or not t.is_contiguous() or t.data_ptr() % 8):
+            raise ValueError(f"{what}: {name} must be a contiguous int64 [{F}, {L}] tensor on {dev}")
+    pm = _photon_map(mask, n, dev, "mask", what)
+    plan = roi_plan((P, H, W), rc, dev)
+    C = _ext.load()
+    s = _ext.stream_handle(stream)
+    for a, b in _chunks(F):
+        C.roi([_ptr(t) for t in frames[a:b]], plan, lo, hi, S, pm, _ptr(rows[a:b]),
+              0 if proj_x is None else _ptr(proj_x[a:b]), 0 if proj_y is None else _ptr(proj_y[a:b]), s)
 
 
 # elements per chunk of the K-10 scan (csrc/kernels.h kSparseChunk): one directory entry per chunk

@@ -986,3 +986,133 @@ def droplet_reference(frames: torch.Tensor, shape, params, mask=None, cap_pix=No
     return DropletList(torch.from_numpy(nact.astype(np.int32)), torch.from_numpy(ndrop.astype(np.int32)),
                        torch.from_numpy(flags), torch.from_numpy(offs), out["label"], out["npix"], out["adu"], out["sy"],
                        out["sx"], out["qmax"])
+
+
+# ---- K-16 ROI statistics -----------------------------------------------------------------------------------------
+# (docs/ARCHITECTURE.md, "ROI: the integer contract")
+ROI_MAX_RECTS = 16
+ROI_VMIN = POWDER_VMIN               # the K-08 window
+ROI_VMAX = POWDER_VMAX
+ROI_FRAC_BITS = 2
+ROI_ROW_WORDS = 8                    # npix, sum, sy, sx, key, 0, 0, 0: one 64-byte line per (frame, rectangle)
+ROI_PROJ = ("none", "x", "y", "both")
+ROI_QMAX_NONE = -2 ** 31             # qmax of a rectangle without a sample (INT32_MIN); its imax is -1
+
+
+def validate_roi_proj(proj, what: str = "roi_stats"):
+    """(wants proj_x, wants proj_y) of a projection selector -- or ValueError."""
+    if proj is None:
+        proj = "none"
+    if proj not in ROI_PROJ:
+        raise ValueError(f"{what}: proj must be one of {', '.join(ROI_PROJ)}, got {proj!r}")
+    return proj in ("x", "both"), proj in ("y", "both")
+
+
+def validate_roi_rects(rects, shape, what: str = "roi_stats") -> np.ndarray:
+    """The rectangles as int32 [R, 5] rows (p, y0, y1, x0, x1), half-open, for frames of ``shape`` = [P, H, W]
+    (or [H, W]: one panel) -- or ValueError.  1 <= R <= 16, 0 <= p < P, 0 <= y0 < y1 <= H, 0 <= x0 < x1 <= W;
+    rectangles are independent (they may overlap or be equal)."""
+    P, H, W = photon_shape(shape, what)
+    try:
+        a = np.asarray(rects.cpu() if isinstance(rects, torch.Tensor) else rects)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: the rectangles must be an integer [R, 5] array") from None
+    if a.dtype == object or a.ndim != 2 or a.shape[1] != 5 or not (np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"{what}: the rectangles must be an integer [R, 5] array of (p, y0, y1, x0, x1), got "
+                         f"{a.dtype} {list(a.shape)}")
+    if not 1 <= a.shape[0] <= ROI_MAX_RECTS:
+        raise ValueError(f"{what}: {a.shape[0]} rectangles; 1 .. {ROI_MAX_RECTS} are possible")
+    a = a.astype(np.int64)
+    for r, (p, y0, y1, x0, x1) in enumerate(a.tolist()):
+        if not (0 <= p < P and 0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+            raise ValueError(f"{what}: rectangle {r} = (p={p}, y={y0}:{y1}, x={x0}:{x1}) is empty or lies outside "
+                             f"frames of shape {(P, H, W)}")
+    return np.ascontiguousarray(a.astype(np.int32))
+
+
+def roi_offsets(rects: np.ndarray):
+    """(offx, offy): int64 [R + 1] running sums of the rectangles' widths and heights."""
+    r = np.asarray(rects, dtype=np.int64)
+    return (np.concatenate([[0], np.cumsum(r[:, 4] - r[:, 3])]).astype(np.int64),
+            np.concatenate([[0], np.cumsum(r[:, 2] - r[:, 1])]).astype(np.int64))
+
+
+def validate_roi_params(vmin, vmax, frac_bits, rects=None, what: str = "roi_stats"):
+    """(vmin, vmax) as the float32 values the kernel sees, frac_bits as a Python int and Q = ceil(max(|vmin|,
+    |vmax|) * 2^S) -- or ValueError: the window must be finite with vmin <= vmax, 0 <= S <= 16, Q < 2^31 (q is an
+    int32) and, for every rectangle of ``rects`` (validated int [R, 5]), Q * area * max(y1 - 1, x1 - 1, 1) <=
+    2^63 - 1 (the int64 moments)."""
+    lo, hi, S, _thr, Q, _mf = validate_powder_params(vmin, vmax, frac_bits, 0.0, what)
+    if rects is not None:
+        for r, (_p, y0, y1, x0, x1) in enumerate(np.asarray(rects).tolist()):
+            worst = Q * (y1 - y0) * (x1 - x0) * max(y1 - 1, x1 - 1, 1)
+            if worst > 2 ** 63 - 1:
+                raise ValueError(f"{what}: rectangle {r}: Q * area * max(y1 - 1, x1 - 1, 1) = {worst} must stay at or "
+                                 f"below 2^63 - 1 (the int64 moments sy / sx); narrow the window or lower frac_bits")
+    return lo, hi, S, Q
+
+
+def roi_key_decode(key):
+    """(qmax int32, imax int32) of key words (any shape; int64 bit patterns or uint64): the largest q and the
+    LOWEST frame index that attains it; INT32_MIN and -1 where key == 0 (no sample)."""
+    k = np.asarray(key.cpu() if isinstance(key, torch.Tensor) else key)
+    k = np.ascontiguousarray(k).view(np.uint64) if k.dtype == np.int64 else k.astype(np.uint64)
+    none = k == 0
+    q = ((k >> np.uint64(32)).astype(np.int64) - 2 ** 31)
+    i = 0xFFFFFFFF - (k & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    return (np.where(none, ROI_QMAX_NONE, q).astype(np.int32), np.where(none, -1, i).astype(np.int32))
+
+
+def roi_stats_reference(frames: torch.Tensor, shape, rects, vmin: float, vmax: float, frac_bits: int, mask=None,
+                        proj="none"):
+    """K-16 golden: per frame and rectangle the integer statistics of the contract.  ``frames``: [F, ...] float32
+    of ``shape`` = [P, H, W] (or [H, W]); ``rects``: int [R, 5] of (p, y0, y1, x0, x1); ``mask``: uint8 [n] or
+    None, non-zero = keep.  A pixel counts iff the mask keeps it and vmin <= v <= vmax as float32 (NaN fails, +-inf
+    is outside); q = int64(round_half_even(v * 2^S)).  Returns ``(rows, proj_x, proj_y)``: rows int64 [F, R, 8] =
+    npix, sum q, sum q * y, sum q * x, key, 0, 0, 0 (y, x inside the panel; key the uint64 bit pattern of the
+    maximum of ((uint32) q ^ 0x80000000) << 32 | (0xFFFFFFFF - idx), 0 without a sample); proj_x int64 [F, Lx] and
+    proj_y int64 [F, Ly], the rectangles' column and row sums one after the other (zero columns when ``proj``
+    does not select the axis)."""
+    what = "roi_stats"
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.float32:
+        raise ValueError(f"{what}: frames must be a float32 tensor, got {getattr(frames, 'dtype', type(frames))}")
+    F = int(frames.shape[0]) if frames.dim() >= 1 else 0
+    if F < 1:
+        raise ValueError(f"{what}: no frames")
+    P, H, W = photon_shape(shape, what)
+    n = P * H * W
+    rc = validate_roi_rects(rects, (P, H, W), what)
+    lo, hi, S, _Q = validate_roi_params(vmin, vmax, frac_bits, rc, what)
+    want_x, want_y = validate_roi_proj(proj, what)
+    x = frames.detach().cpu().reshape(F, -1)
+    if x.shape[1] != n:
+        raise ValueError(f"{what}: frames of {x.shape[1]} elements for the shape {(P, H, W)}")
+    x = x.reshape(F, P, H, W)
+    mask, _roi, _R = validate_photon_maps((P, H, W), mask, None, None, what)
+    keep = None if mask is None else torch.from_numpy(mask != 0).reshape(P, H, W)
+    R = rc.shape[0]
+    rows = np.zeros((F, R, ROI_ROW_WORDS), dtype=np.int64)
+    px, py = [], []
+    for r, (p, y0, y1, x0, x1) in enumerate(rc.tolist()):
+        sub = x[:, p, y0:y1, x0:x1]
+        ok = (sub >= lo) & (sub <= hi)
+        if keep is not None:
+            ok &= keep[p, y0:y1, x0:x1]
+        q = torch.where(ok, torch.round(torch.where(ok, sub, torch.zeros_like(sub)) * float(2 ** S)),
+                        torch.zeros_like(sub)).to(torch.int64)
+        ys = torch.arange(y0, y1, dtype=torch.int64).reshape(1, -1, 1)
+        xs = torch.arange(x0, x1, dtype=torch.int64).reshape(1, 1, -1)
+        rows[:, r, 0] = ok.sum(dim=(1, 2)).numpy()
+        rows[:, r, 1] = q.sum(dim=(1, 2)).numpy()
+        rows[:, r, 2] = (q * ys).sum(dim=(1, 2)).numpy()
+        rows[:, r, 3] = (q * xs).sum(dim=(1, 2)).numpy()
+        idx = ((p * H + ys) * W + xs).numpy().astype(np.uint64)
+        key = ((q.numpy() + 2 ** 31).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - idx)
+        key = np.where(ok.numpy(), key, np.uint64(0)).reshape(F, -1).max(axis=1)
+        rows[:, r, 4] = key.view(np.int64)
+        if want_x:
+            px.append(q.sum(dim=1))
+        if want_y:
+            py.append(q.sum(dim=2))
+    empty = torch.zeros((F, 0), dtype=torch.int64)
+    return (torch.from_numpy(rows), torch.cat(px, dim=1) if px else empty, torch.cat(py, dim=1) if py else empty)

@@ -20,7 +20,9 @@ maximum of the calibrated frames (K-11), split into misses and hits by the same 
 PixelHistConsumer keeps the exact per-pixel spectrum of the calibrated frames (K-12); PhotonConsumer counts
 photons per pixel with psana's neighbour merge (K-13): run maps and the per-frame P(k) of up to 8 ROIs;
 DropletConsumer writes every frame's connected clusters of pixels above a threshold as integer rows (K-14);
-CubeConsumer keeps the exact per-pixel run sums of the calibrated frames per bin of a per-event scalar (K-15).
+CubeConsumer keeps the exact per-pixel run sums of the calibrated frames per bin of a per-event scalar (K-15);
+RoiConsumer keeps per frame the sum, moments, maximum and projections of up to 16 rectangles, read from the
+rectangles alone (K-16).
 """
 from __future__ import annotations
 
@@ -1538,6 +1540,145 @@ class PhotonConsumer(_BatchConsumer):
                                      rank=[m[0] for m in meta], idx=[m[1] for m in meta], gevt=[m[2] for m in meta],
                                      photon_energy=[float("nan") if m[3] is None else float(m[3]) for m in meta],
                                      pk=pk.copy(), tot=tot.copy())
+
+
+class RoiConsumer(_BatchConsumer):
+    """Consumer engine: batches of leased slots -> K-16 ROI statistics (csrc/roi.hip) -> stream-ordered release.
+
+    Per frame and rectangle: the pixels inside the value window, their sum, first moments, maximum with its
+    position and, when selected, the projections onto x and y -- integers, equal to the golden model word for
+    word.  Only the rectangles are read.  The frames never leave the GPU: the per-frame rows (64 bytes per
+    rectangle plus the projections) go to pinned host memory stream-ordered.  There is no run accumulator, so
+    the streams share nothing and a run has no frame bound."""
+
+    name = "roi"
+    wants_meta = True
+
+    def __init__(self, endpoint: QueueEndpoint, frame_shape, rects, vmin: Optional[float] = None,
+                 vmax: Optional[float] = None, frac_bits: Optional[int] = None, proj: str = "none", mask=None,
+                 detector: str = "", layout: str = "calib", batch: Optional[int] = None,
+                 stream_kind: str = CONSUMER_STREAM_KIND, streams: int = CONSUMER_STREAMS,
+                 ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
+        """frame_shape: the shape of a (calibrated) frame, [P, H, W] or [H, W].  rects: a
+        :class:`psana_ray_amd.roi.RoiSet`, or int rows (p, y0, y1, x0, x1) -- (y0, y1, x0, x1) for 2-D frames.
+        mask: a uint8 array of a frame's elements (non-zero = keep), or None.  check_ring=False: the queue
+        carries RAW frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
+        from .ops import reference as _ref
+        from .roi import RoiSet, mask_sha256
+
+        self.shape = tuple(int(s) for s in frame_shape)
+        self.phw = _ref.photon_shape(self.shape, "roi")
+        self.n = int(np.prod(self.phw))
+        self.roiset = rects if isinstance(rects, RoiSet) else RoiSet(rects, self.shape)
+        if self.roiset.phw != self.phw:
+            raise ValueError(f"roi: rectangles for frames of {self.roiset.frame_shape}, these are {self.shape}")
+        self.rects = self.roiset.rects
+        self.n_roi = self.roiset.R
+        self.vmin, self.vmax, self.frac_bits, _Q = _ref.validate_roi_params(
+            _ref.ROI_VMIN if vmin is None else vmin, _ref.ROI_VMAX if vmax is None else vmax,
+            _ref.ROI_FRAC_BITS if frac_bits is None else frac_bits, self.rects, "roi")
+        self.proj = "none" if proj is None else proj
+        self._want_x, self._want_y = _ref.validate_roi_proj(self.proj, "roi")
+        self._mask_np, _roi, _R = _ref.validate_photon_maps(self.phw, mask, None, None, "roi")
+        self.mask_sha256 = mask_sha256(self.phw, self._mask_np)
+        self.Lx = int(self.roiset.offx[-1]) if self._want_x else 0
+        self.Ly = int(self.roiset.offy[-1]) if self._want_y else 0
+        self.row_bytes = self.roiset.row_bytes(self.proj)
+        self.detector, self.layout = str(detector), str(layout)
+        if check_ring:
+            if endpoint.ring.dtype != torch.float32:
+                raise ValueError(f"roi: the queue carries {endpoint.ring.dtype} frames, ROI statistics need "
+                                 "calibrated float32 ones")
+            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
+                raise ValueError(f"roi: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        # per batch: (rows int64 [n, R, 8], proj_x int64 [n, Lx], proj_y int64 [n, Ly], [(rank, idx, gevt,
+        # photon_energy), ...]); on the GPU path the arrays are pinned host tensors filled asynchronously: valid
+        # after sync_streams()
+        self.results = []
+        if self.gpu:
+            dev, B, R = self.device, self.batch, self.n_roi
+            self._rows = torch.zeros((self._nbuf, B, R, _ref.ROI_ROW_WORDS), dtype=torch.int64, device=dev)
+            self._px = torch.zeros((self._nbuf, B, self.Lx), dtype=torch.int64, device=dev) if self._want_x else None
+            self._py = torch.zeros((self._nbuf, B, self.Ly), dtype=torch.int64, device=dev) if self._want_y else None
+            self._mask = None if self._mask_np is None else torch.from_numpy(self._mask_np).to(dev)
+            self._plan = kernels.roi_plan(self.phw, self.rects, dev)
+
+    def _check_batch(self, n):
+        if n > self.batch:
+            raise ValueError(f"roi: {n} frames in a batch of at most {self.batch}")
+
+    def process_frames(self, frames, meta):
+        """Process ``frames`` (tensors of n elements on this consumer's device, issued on the current stream)
+        that are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank, idx, gevt,
+        photon_energy)``.  GPU: returns the consumer stream the batch runs on."""
+        return super().process_frames(frames, [tuple(m) + (None,) * (4 - len(m)) for m in meta])
+
+    def _meta_of(self, recs):
+        # a slot header carries NaN for "no photon energy", a queue item None
+        return [(r.rank, r.idx, r.gevt, None if r.photon_energy != r.photon_energy else r.photon_energy)
+                for r in recs]
+
+    def _launch_slots(self, C, slots, b, k, st):
+        C.roi_slots(self.ep.pool, self.ep._slot_bytes, slots, self._plan, self.vmin, self.vmax, self.frac_bits,
+                    0 if self._mask is None else int(self._mask.data_ptr()), int(self._rows[b].data_ptr()),
+                    0 if self._px is None else int(self._px[b].data_ptr()),
+                    0 if self._py is None else int(self._py[b].data_ptr()), int(st.cuda_stream))
+
+    def _launch_tensors(self, frames, b, k, st):
+        n = len(frames)
+        kernels.roi_stats([t.reshape(-1) for t in frames], self.phw, self.rects, self.vmin, self.vmax, self.frac_bits,
+                          self._rows[b, :n], None if self._px is None else self._px[b, :n],
+                          None if self._py is None else self._py[b, :n], mask=self._mask, stream=st)
+
+    def _launched(self, b, n, st, meta):
+        """The batch's per-frame rows go to PINNED HOST memory by asynchronous copies on the current
+        (consumer) stream; the kept tensors are valid after :meth:`sync_streams`."""
+        from .ops.reference import ROI_ROW_WORDS
+
+        rows = torch.empty((n, self.n_roi, ROI_ROW_WORDS), dtype=torch.int64, pin_memory=True)
+        rows.copy_(self._rows[b, :n], non_blocking=True)
+        px = py = None
+        if self._px is not None:
+            px = torch.empty((n, self.Lx), dtype=torch.int64, pin_memory=True)
+            px.copy_(self._px[b, :n], non_blocking=True)
+        if self._py is not None:
+            py = torch.empty((n, self.Ly), dtype=torch.int64, pin_memory=True)
+            py.copy_(self._py[b, :n], non_blocking=True)
+        self.results.append((rows, px, py, meta))
+
+    def _reference(self, frames, meta):
+        from .ops import reference
+
+        x = torch.stack([t.reshape(-1) for t in frames])
+        rows, px, py = reference.roi_stats_reference(x, self.phw, self.rects, self.vmin, self.vmax, self.frac_bits,
+                                                     self._mask_np, self.proj)
+        self.results.append((rows, px if self._want_x else None, py if self._want_y else None, list(meta)))
+
+    def synchronize(self) -> int:
+        """Wait for every batch; returns the frames processed."""
+        if self.gpu:
+            self.sync_streams()
+        return self.frames
+
+    def stats(self):
+        """The (synchronised) run as a :class:`psana_ray_amd.roi.RoiFrames`, rows in processing order."""
+        from .ops.reference import ROI_ROW_WORDS
+        from .roi import RoiFrames
+
+        self.synchronize()
+        meta = [m for *_, ms in self.results for m in ms]
+        as_np = lambda t: t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)   # noqa: E731
+
+        def cat(i):   # None: nothing kept (an axis not selected, or no batch yet) -> RoiFrames makes it empty
+            parts = [as_np(r[i]) for r in self.results if r[i] is not None]
+            return np.concatenate(parts).copy() if parts else None
+
+        rows = cat(0) if self.results else np.zeros((0, self.n_roi, ROI_ROW_WORDS), np.int64)
+        return RoiFrames.from_rows(self.detector, self.layout, self.shape, self.vmin, self.vmax, self.frac_bits,
+                                   self.proj, self.rects, self.mask_sha256, rows, cat(1), cat(2),
+                                   rank=[m[0] for m in meta], idx=[m[1] for m in meta], gevt=[m[2] for m in meta],
+                                   photon_energy=[float("nan") if m[3] is None else float(m[3]) for m in meta])
 
 
 class DropletConsumer(_BatchConsumer):

@@ -77,7 +77,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--data_dir", type=str, default=None, help="raw-run files directory (or $PSANA_RAY_DATA)")
     g.add_argument("--chunk", type=int, default=64, help="frames per H2D copy / kernel launch (<= 64)")
     g.add_argument("--route", type=str, default="balanced", choices=["balanced", "local_first", "spread"])
-    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets", "cube"],
+    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets", "cube", "roi"],
                    help="also consume on every producer rank (co-located consumer, BASELINE config 5): the K-07 "
                         "peak finder, the K-08 radial profile (default binning of psana-ray-consumer), the K-09 "
                         "dark statistics (needs --mode raw; --out_dark writes the file), or the K-10 zero "
@@ -89,7 +89,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "--adu_per_photon ... --photon_roi as for psana-ray-consumer --task photons), or the K-14 "
                         "droplets (--out_droplets writes the file; --drop_thr_low ... --drop_mask as for "
                         "psana-ray-consumer --task droplets), or the K-15 cube (--out_cube writes the file; "
-                        "--cube_by ... --cube_frac_bits as for psana-ray-consumer --task cube)")
+                        "--cube_by ... --cube_frac_bits as for psana-ray-consumer --task cube), or the K-16 ROI "
+                        "statistics (--out_roi writes the file; --roi ... --roi_mask as for psana-ray-consumer --task "
+                        "roi)")
+    g.add_argument("--out_roi", type=str, default=None,
+                   help="--consumer_task roi: write the rank's per-frame ROI records (psana_ray_amd.roi.RoiFrames .npz) "
+                        "here")
     g.add_argument("--out_cube", type=str, default=None,
                    help="--consumer_task cube: write the rank's cube (psana_ray_amd.cube.CubeStats .npz) here")
     g.add_argument("--out_droplets", type=str, default=None,
@@ -136,7 +141,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--local", action="store_true",
                    help="single-process queue: no rendezvous; requires --consumer_task (no external consumers)")
     from .consumer import (add_cube_arguments, add_droplet_arguments, add_hist_arguments, add_photon_arguments,
-                           add_powder_arguments, add_sparse_arguments)
+                           add_powder_arguments, add_roi_arguments, add_sparse_arguments)
 
     add_sparse_arguments(parser)
     add_powder_arguments(parser)
@@ -144,6 +149,7 @@ def build_parser() -> argparse.ArgumentParser:
     add_photon_arguments(parser)
     add_droplet_arguments(parser)
     add_cube_arguments(parser)
+    add_roi_arguments(parser)
     return parser
 
 
@@ -307,7 +313,7 @@ def main(argv=None) -> int:
                       "or a co-located --consumer_task")
             return 2
         mode = Mode.raw   # frames travel raw; DataReader applies read_mode
-    if args.consumer_task in ("radial", "sparse", "powder", "hist", "photons", "droplets", "cube") and (mode == Mode.raw or int(args.panel_shards) > 1):
+    if args.consumer_task in ("radial", "sparse", "powder", "hist", "photons", "droplets", "cube", "roi") and (mode == Mode.raw or int(args.panel_shards) > 1):
         log.error("--consumer_task %s needs whole calibrated frames (not --mode raw / --panel_shards)",
                   args.consumer_task)
         return 2
@@ -315,7 +321,8 @@ def main(argv=None) -> int:
         log.error("--consumer_task dark needs whole raw frames (--mode raw, no --panel_shards)")
         return 2
     for flag, task in (("out_sparse", "sparse"), ("out_dark", "dark"), ("out_powder", "powder"),
-                       ("out_hist", "hist"), ("out_photons", "photons"), ("out_droplets", "droplets"), ("out_cube", "cube")):
+                       ("out_hist", "hist"), ("out_photons", "photons"), ("out_droplets", "droplets"), ("out_cube", "cube"),
+                       ("out_roi", "roi")):
         if getattr(args, flag) is not None and args.consumer_task != task:
             log.error("--%s belongs to --consumer_task %s", flag, task)
             return 2
@@ -333,6 +340,14 @@ def main(argv=None) -> int:
     if args.consumer_task == "droplets" and args.drop_thr_low is None:
         log.error("--consumer_task droplets needs --drop_thr_low")
         return 2
+    if args.consumer_task == "roi":   # the rectangles are checked before anything starts
+        from .consumer import roi_check_flags
+
+        try:
+            roi_check_flags(args)
+        except (ValueError, OSError) as e:
+            log.error("--consumer_task roi: %s", e)
+            return 2
     shards = int(args.panel_shards)
     if shards > 1:
         from .source.shard import PanelShardSource, shard_layout
@@ -454,7 +469,7 @@ def main(argv=None) -> int:
             # consumer thread, at the end of the stream), report(result or None, frames consumed) after the join
             each = None
 
-            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder / .hist / .photons / .droplets / .cube merge)
+            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder / .hist / .photons / .droplets / .cube / .roi merge)
                 root, ext = os.path.splitext(path)
                 return path if size == 1 else f"{root}.r{rank}{ext}"
 
@@ -607,6 +622,23 @@ def main(argv=None) -> int:
                         path = rank_path(args.out_cube)
                         cs.save(path)
                         log.info("Rank %d: cube written to %s", rank, path)
+            elif args.consumer_task == "roi":
+                try:
+                    from .consumer import roi_consumer, roi_final_line, roi_start_line
+
+                    cons = roi_consumer(args, ep, frame_shape, args.detector_name, mode.value)
+                except (ValueError, OSError) as e:
+                    log.error("--consumer_task roi: %s", e)
+                    return 2
+                print(roi_start_line(rank, cons), flush=True)
+                finish = cons.stats
+
+                def report(rf, consumed):
+                    print(roi_final_line(rank, cons, args.detector_name, mode.value), flush=True)
+                    if rf is not None and args.out_roi:
+                        path = rank_path(args.out_roi)
+                        rf.save(path)
+                        log.info("Rank %d: ROI records written to %s", rank, path)
             else:
                 cons = PeakFinderConsumer(ep, frame_shape, PeakFinderParams())
                 finish = cons.synchronize
