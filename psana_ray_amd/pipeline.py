@@ -22,7 +22,10 @@ photons per pixel with psana's neighbour merge (K-13): run maps and the per-fram
 DropletConsumer writes every frame's connected clusters of pixels above a threshold as integer rows (K-14);
 CubeConsumer keeps the exact per-pixel run sums of the calibrated frames per bin of a per-event scalar (K-15);
 RoiConsumer keeps per frame the sum, moments, maximum and projections of up to 16 rectangles, read from the
-rectangles alone (K-16).
+rectangles alone (K-16).  The batch loop is written once, in _BatchConsumer.  _RunAccumulator (dark,
+powder, hist, photons, cube) adds the frame bound of a run and one accumulator set per stream, with the one
+combine of the sets in ``synchronize()``; _PackedRows (sparse, droplets) adds the header row, the data
+columns and the two-step drain to pinned host memory, with its ordering rule.
 """
 from __future__ import annotations
 
@@ -502,8 +505,10 @@ class _BatchConsumer:
       * the slot headers (a host read) are taken before the release.
     CPU endpoints run the golden models (ops.reference)."""
 
-    name = ""            # the trace range of a batch is "consumer.<name>_batch"
+    name = ""            # the trace range of a batch is "consumer.<name>_batch", errors start "<name>: "
     wants_meta = False   # True: _launched(b, n, st, meta) runs after every launch (results are kept)
+    meta_fields = 3      # 4: the meta tuples end with the photon energy (None: the event has none)
+    batch_refusal = True   # process_frames refuses more than ``batch`` frames
 
     def __init__(self, endpoint: QueueEndpoint, batch: Optional[int], ranks_per_gpu: Optional[int], streams: int,
                  stream_kind: str):
@@ -570,12 +575,14 @@ class _BatchConsumer:
 
     def process_frames(self, frames, meta=None):
         """Process ``frames`` (tensors on this consumer's device, issued on the current stream) that
-        are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank, idx, gevt)``.
-        GPU: returns the consumer stream the batch runs on."""
+        are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank, idx, gevt)``,
+        with ``meta_fields = 4`` ``(rank, idx, gevt, photon_energy)`` (shorter tuples are padded with
+        None).  GPU: returns the consumer stream the batch runs on."""
         n = len(frames)
         if n == 0:
             return None
         self._check_batch(n)
+        meta = self._pad_meta(meta)
         st = None
         if self.gpu:
             b, k, st = self._next()
@@ -604,6 +611,58 @@ class _BatchConsumer:
         for st in self.streams:
             st.synchronize()
 
+    # ------------------------------------------------------------------ meta tuples
+    def _meta_of(self, recs):
+        """The meta tuples (``meta_fields`` long) of queue items or slot headers."""
+        if self.meta_fields == 3:
+            return [(r.rank, r.idx, r.gevt) for r in recs]
+        # a slot header carries NaN for "no photon energy", a queue item None
+        return [(r.rank, r.idx, r.gevt, None if r.photon_energy != r.photon_energy else r.photon_energy)
+                for r in recs]
+
+    def _pad_meta(self, meta):
+        """Caller-made meta tuples, padded with None to ``meta_fields``."""
+        if meta is None or self.meta_fields == 3:
+            return meta
+        return [tuple(m) + (None,) * (self.meta_fields - len(m)) for m in meta]
+
+    @staticmethod
+    def _meta_columns(meta) -> dict:
+        """4-field meta tuples as the columns every result file has (NaN: no photon energy)."""
+        return {"rank": [m[0] for m in meta], "idx": [m[1] for m in meta], "gevt": [m[2] for m in meta],
+                "photon_energy": [float("nan") if m[3] is None else float(m[3]) for m in meta]}
+
+    # ------------------------------------------------------------------ helpers of the constructors and of stats()
+    def _check_ring(self, endpoint: QueueEndpoint, needs: str, dtype=torch.float32, of: Optional[str] = None):
+        """Raise unless the ring carries ``dtype`` frames of ``self.n`` elements.  It needs ``name``,
+        ``n`` and ``shape`` only, so an engine calls it before the base constructor makes streams."""
+        ring = endpoint.ring
+        if ring.dtype != dtype:
+            raise ValueError(f"{self.name}: the queue carries {ring.dtype} frames, {needs}")
+        if int(np.prod(ring.frame_shape)) != self.n:
+            raise ValueError(f"{self.name}: queue frames {tuple(ring.frame_shape)} are not the {self.n} pixels of "
+                             + (of or f"a frame of {self.shape}"))
+
+    def _keep_pinned(self, bufs, b: int, n: int, meta):
+        """_launched: rows ``[b, :n]`` of the device buffers ``bufs`` (None stays None) go to fresh PINNED
+        HOST tensors by asynchronous copies on the current (consumer) stream, so a long run keeps
+        nothing in HBM; ``(*hosts, meta)`` joins :attr:`results`, valid after :meth:`sync_streams`."""
+        kept = []
+        for d in bufs:
+            h = None
+            if d is not None:
+                h = torch.empty((n, *d.shape[2:]), dtype=d.dtype, pin_memory=True)
+                h.copy_(d[b, :n], non_blocking=True)
+            kept.append(h)
+        self.results.append((*kept, meta))
+
+    @staticmethod
+    def _cat(parts, empty=None):
+        """stats(): the kept batches (host tensors or arrays; None is skipped) as one fresh array,
+        ``empty`` when there is none."""
+        parts = [p.numpy() if isinstance(p, torch.Tensor) else np.asarray(p) for p in parts if p is not None]
+        return np.concatenate(parts) if parts else empty
+
     # ------------------------------------------------------------------ what a consumer fills in
     def _limit(self, n_max: int) -> int:
         """Frames the next poll may take at most (it may raise instead)."""
@@ -611,10 +670,8 @@ class _BatchConsumer:
 
     def _check_batch(self, n: int):
         """process_frames: raise if a batch of ``n`` frames cannot be taken."""
-
-    def _meta_of(self, recs):
-        """The meta tuples of queue items or slot headers."""
-        return [(r.rank, r.idx, r.gevt) for r in recs]
+        if self.batch_refusal and n > self.batch:
+            raise ValueError(f"{self.name}: {n} frames in a batch of at most {self.batch}")
 
     def _launch_slots(self, C, slots, b: int, k: int, st):
         """The native call(s) on leased ring ``slots``: buffer row b, stream k."""
@@ -635,7 +692,7 @@ class _BatchConsumer:
 
 class _PeakBuffers:
     """The peak finder's (K-07) device buffers and its two calls, for :class:`PeakFinderConsumer`
-    and the hit filter of :class:`SparseFrameConsumer`."""
+    and :class:`_HitFilter`."""
 
     def __init__(self, device, params: PeakFinderParams, shape, batch: int, nbuf: int, n_streams: int):
         B = batch
@@ -667,6 +724,62 @@ class _PeakBuffers:
                          st, total=self.total, scratch=self.scratch[k])
 
 
+class _HitFilter:
+    """The hit filter of :class:`SparseFrameConsumer` and :class:`PowderConsumer`: with ``min_peaks > 0``
+    the peak finder (K-07) runs first on the batch's stream and its per-frame counts are the ``keys``
+    the consumer's kernel compares with ``min_peaks`` ON THE DEVICE -- no host round trip.  With
+    ``min_peaks == 0`` there is no peak finder and no keys.  The constructor only validates (errors
+    start with the owner's ``name``); :meth:`allocate` makes the device buffers once the owner knows
+    its batch."""
+
+    def __init__(self, name: str, shape, min_peaks: int, peak_params: Optional[PeakFinderParams]):
+        self.min_peaks = int(min_peaks)
+        if self.min_peaks < 0:
+            raise ValueError(f"{name}: min_peaks must be >= 0")
+        self.params = peak_params or PeakFinderParams()
+        self.pf = None   # _PeakBuffers (GPU, min_peaks > 0)
+        if self.min_peaks > 0:
+            if len(shape) not in (2, 3):
+                raise ValueError(f"{name}: the hit filter needs 2-D or 3-D frames, got {shape}")
+            if self.params.radius not in (1, 2):
+                raise ValueError(f"{name}: peak finder radius must be 1 or 2")
+            self.shape = tuple(shape) if len(shape) == 3 else (1, *shape)   # (P, H, W)
+
+    def allocate(self, device, batch: int, nbuf: int, n_streams: int):
+        if self.min_peaks > 0:
+            self.pf = _PeakBuffers(device, self.params, self.shape, batch, nbuf, n_streams)
+
+    def peak_dict(self) -> dict:
+        """The peak-finder parameters a result file records ({}: no filter)."""
+        if self.min_peaks <= 0:
+            return {}
+        p = self.params
+        return {"thr_peak": float(p.thr_peak), "son_min": float(p.son_min), "radius": float(p.radius)}
+
+    def keys_slots(self, C, ep, slots, b: int, k: int, st) -> int:
+        """Ring-slot path: launch the peak finder; the device pointer of the counts row (0: no filter)."""
+        if self.pf is None:
+            return 0
+        self.pf.launch_slots(C, ep, slots, b, k, st)
+        return int(self.pf.counts[b].data_ptr())
+
+    def keys_tensors(self, frames, b: int, k: int, st):
+        """Tensor path: launch the peak finder; the counts of the frames (None: no filter)."""
+        if self.pf is None:
+            return None
+        self.pf.launch_tensors(frames, b, k, st)
+        return self.pf.counts[b, :len(frames)]
+
+    def keys_reference(self, x):
+        """CPU: the golden model's counts of the stacked flat frames ``x`` (None: no filter)."""
+        if self.min_peaks <= 0:
+            return None
+        from .ops import reference
+
+        pk, _ = reference.peakfind_reference(x.reshape(x.shape[0], *self.shape), self.params)
+        return torch.tensor([int(p.shape[0]) for p in pk], dtype=torch.int32)
+
+
 class PeakFinderConsumer(_BatchConsumer):
     """Consumer engine: batches of leased slots -> K-07 peak finder -> stream-ordered release.
 
@@ -675,6 +788,7 @@ class PeakFinderConsumer(_BatchConsumer):
     launch's streaming reads."""
 
     name = "peakfind"
+    batch_refusal = False
 
     def __init__(self, endpoint: QueueEndpoint, frame_shape, params: Optional[PeakFinderParams] = None,
                  batch: Optional[int] = None, keep_results: bool = False, stream_kind: str = CONSUMER_STREAM_KIND,
@@ -725,12 +839,13 @@ class RadialProfileConsumer(_BatchConsumer):
     :meth:`synchronize`."""
 
     name = "radial"
+    batch_refusal = False
 
     def __init__(self, endpoint: QueueEndpoint, binning, vmin: Optional[float] = None, vmax: Optional[float] = None,
                  frac_bits: Optional[int] = None, batch: Optional[int] = None, keep_results: bool = False,
                  stream_kind: str = CONSUMER_STREAM_KIND, streams: int = CONSUMER_STREAMS,
                  ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
-        """check_ring=False: the queue carries RAW frames that the caller calibrates before
+        """check_ring=False: the ring holds RAW frames that the caller calibrates before
         :meth:`process_frames` (``--calibrate_on_read``), so the ring's frame shape is not the binning's."""
         from .models import radial as _radial
         from .ops.reference import radial_bound_ok
@@ -779,12 +894,9 @@ class RadialProfileConsumer(_BatchConsumer):
                                self.profile[b, :n], self.vmin, self.vmax, self.frac_bits, run=self.run, stream=st)
 
     def _launched(self, b, n, st, meta):
-        """keep_results, GPU: the batch's profiles go to PINNED HOST memory by an asynchronous copy on
-        the current (consumer) stream, so a long run keeps nothing in HBM (64 frames x 1024 bins =
-        256 KiB of host memory per batch).  The kept tensors are valid after :meth:`sync_streams`."""
-        host = torch.empty((n, self.nbins), dtype=torch.float32, pin_memory=True)
-        host.copy_(self.profile[b, :n], non_blocking=True)
-        self.results.append((host, meta))
+        """keep_results, GPU: the batch's profiles go to pinned host memory (64 frames x 1024 bins =
+        256 KiB per batch)."""
+        self._keep_pinned((self.profile,), b, n, meta)
 
     def _reference(self, frames, meta):
         from .ops import reference
@@ -814,17 +926,105 @@ class RadialProfileConsumer(_BatchConsumer):
         return mean_profile(self.run_sum, self.run_count, self.frac_bits)
 
 
-class DarkStatsConsumer(_BatchConsumer):
+_Field = collections.namedtuple("_Field", "name shape dev host init op", defaults=(0, "sum"))
+
+
+class _RunAccumulator(_BatchConsumer):
+    """What the engines with exact integer run sums share (dark, powder, hist, photons, cube): the frame
+    bound of a run, and one accumulator set per consumer stream.
+
+    Their kernels own a pixel per launch and use no global atomics on the run sums, so every stream
+    has its OWN set: set k is only ever touched by launches on stream k, and two streams never
+    read-modify-write the same words.  Every value is an integer, so the sets combine exactly in any
+    order; a count is at most the frames of the run, which ``max_frames`` keeps inside its int32.
+    A subclass sets ``max_frames`` and whatever :meth:`_fields` reads BEFORE this constructor, which
+    builds
+      * ``_acc``: per stream the tuple of device tensors in field order (one field: the bare tensor);
+      * ``_host``: the host copy ``{name: array}`` at its initial values -- the CPU path adds the
+        golden model's outputs to it (:meth:`_add`), the GPU path replaces it in :meth:`synchronize`,
+        the only place where the sets meet."""
+
+    bound_text = "{}"   # how "... would take the run past" goes on; {}: max_frames
+
+    def __init__(self, endpoint: QueueEndpoint, batch: Optional[int], ranks_per_gpu: Optional[int], streams: int,
+                 stream_kind: str):
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        self._spec = tuple(self._fields())
+        self._host = {f.name: np.full(f.shape, f.init, f.host) for f in self._spec}
+        if self.gpu:
+            sets = [tuple(torch.full(f.shape, f.init, dtype=f.dev, device=self.device) for f in self._spec)
+                    for _ in self.streams]
+            self._acc = sets if len(self._spec) > 1 else [s[0] for s in sets]
+
+    def _check_bound(self, n: int):
+        if self.frames + n > self.max_frames:
+            raise ValueError(f"{self.name}: {self.frames} + {n} frames would take the run past "
+                             + self.bound_text.format(self.max_frames))
+
+    def _check_batch(self, n: int):
+        super()._check_batch(n)
+        self._check_bound(n)
+
+    def _limit(self, n_max: int) -> int:
+        self._check_bound(1)   # before any lease
+        return max(1, min(n_max, self.max_frames - self.frames))
+
+    @staticmethod
+    def _fold(total, part, op: str):
+        """``total += part`` or, for "max", their element-wise maximum, in place (tensors of one device)."""
+        torch.maximum(total, part, out=total) if op == "max" else total.add_(part)
+
+    def _add(self, parts):
+        """CPU: the golden model's outputs (tensors in field order) join the host copy."""
+        for f, part in zip(self._spec, parts):
+            self._fold(torch.from_numpy(self._host[f.name]), part, f.op)
+
+    def synchronize(self):
+        """Wait for every batch, combine the per-stream sets ON THE DEVICE one field at a time (a
+        temporary is freed before the next is made: at most one field of one set lives beside the
+        sets) and copy the one result to the host, where it takes the field's host dtype.  Returns
+        :meth:`_result`."""
+        if self.gpu:
+            self.sync_streams()
+            sets = [a if isinstance(a, tuple) else (a,) for a in self._acc]
+            host = {}
+            with torch.cuda.device(self.device):
+                for i, f in enumerate(self._spec):
+                    total = sets[0][i]
+                    if len(sets) > 1:
+                        total = total.clone()
+                        for s in sets[1:]:
+                            self._fold(total, s[i], f.op)
+                    host[f.name] = total.cpu().numpy().astype(f.host, copy=False)
+                    del total
+            self._host = host
+        return self._result()
+
+    # ------------------------------------------------------------------ what a run accumulator fills in
+    def _fields(self):
+        """The accumulator's fields, stated once: ``_Field(name, shape, device dtype, host dtype,
+        initial value = 0, op = "sum" | "max")`` in the order of the kernel's arguments."""
+        raise NotImplementedError
+
+    def _result(self):
+        """What :meth:`synchronize` returns: the host copy (one field: the bare array)."""
+        return self._host if len(self._spec) > 1 else self._host[self._spec[0].name]
+
+
+class DarkStatsConsumer(_RunAccumulator):
     """Consumer engine: batches of leased RAW uint16 slots -> K-09 dark statistics (csrc/dark.hip) ->
     stream-ordered release.
 
     Per run: per-pixel, per-candidate count / sum / sum of squares of the raw ADU inside the window
-    ``[adu_lo, adu_hi]`` -- integers, so the result is exact in any frame order.  The kernel owns a
-    pixel per launch and uses no atomics, so every consumer stream has its OWN accumulator set (two
-    streams never read-modify-write the same words; the buffer row is not used);
-    :meth:`synchronize` adds the sets on the host."""
+    ``[adu_lo, adu_hi]`` -- integers, so the result is exact in any frame order.  One accumulator set
+    per consumer stream (:class:`_RunAccumulator`; the buffer row is not used)."""
 
     name = "dark"
+    batch_refusal = False
+    bound_text = "2^31 - 1 (the int32 count)"
+    cnt = property(lambda self: self._host["cnt"])   # the (synchronised) run, int64 [NC, n] each
+    sum = property(lambda self: self._host["sum"])
+    sq = property(lambda self: self._host["sq"])
 
     def __init__(self, endpoint: QueueEndpoint, spec, adu_lo: int = 0, adu_hi: Optional[int] = None,
                  batch: Optional[int] = None, stream_kind: str = CONSUMER_STREAM_KIND,
@@ -836,32 +1036,18 @@ class DarkStatsConsumer(_BatchConsumer):
             spec.kernel_kind, adu_lo, 65535 if adu_hi is None else adu_hi, "dark")
         self.nc = int(spec.n_candidates)
         self.n = int(spec.npix)
-        if endpoint.ring.dtype != torch.uint16:
-            raise ValueError(f"dark: the queue carries {endpoint.ring.dtype} frames, dark statistics need raw uint16")
-        if int(np.prod(endpoint.ring.frame_shape)) != self.n:
-            raise ValueError(f"dark: queue frames {tuple(endpoint.ring.frame_shape)} are not the {self.n} pixels "
-                             f"of {spec.name}")
-        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        self._check_ring(endpoint, "dark statistics need raw uint16", torch.uint16, spec.name)
         self.max_frames = DARK_MAX_FRAMES
-        self.cnt = np.zeros((self.nc, self.n), np.int64)
-        self.sum = np.zeros((self.nc, self.n), np.int64)
-        self.sq = np.zeros((self.nc, self.n), np.int64)
-        if self.gpu:
-            # one accumulator set per stream; set k is only ever touched by launches on stream k
-            self._acc = [(torch.zeros((self.nc, self.n), dtype=torch.int32, device=self.device),
-                          torch.zeros((self.nc, self.n), dtype=torch.int64, device=self.device),
-                          torch.zeros((self.nc, self.n), dtype=torch.int64, device=self.device))
-                         for _ in self.streams]
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
 
-    def _check_bound(self, n: int):
-        if self.frames + n > self.max_frames:
-            raise ValueError(f"dark: {self.frames} + {n} frames would take the run past 2^31 - 1 (the int32 count)")
+    def _fields(self):
+        s = (self.nc, self.n)
+        return (_Field("cnt", s, torch.int32, np.int64), _Field("sum", s, torch.int64, np.int64),
+                _Field("sq", s, torch.int64, np.int64))
 
-    _check_batch = _check_bound
-
-    def _limit(self, n_max):
-        self._check_bound(1)   # before any lease
-        return max(1, min(n_max, self.max_frames - self.frames))
+    def _result(self):
+        """``(cnt int64 [NC, n], sum int64 [NC, n], sq int64 [NC, n], frames)``."""
+        return self.cnt, self.sum, self.sq, self.frames
 
     def _launch_slots(self, C, slots, b, k, st):
         cnt, s, q = self._acc[k]
@@ -876,25 +1062,8 @@ class DarkStatsConsumer(_BatchConsumer):
     def _reference(self, frames, meta):
         from .ops import reference
 
-        c, s, q = reference.dark_accumulate_reference(torch.stack([t.reshape(-1) for t in frames]), self.kind,
-                                                      self.adu_lo, self.adu_hi)
-        self.cnt += c.numpy()
-        self.sum += s.numpy()
-        self.sq += q.numpy()
-
-    def synchronize(self):
-        """Wait for every batch and add the per-stream accumulator sets on the host (exact).  Returns
-        ``(cnt int64 [NC, n], sum int64 [NC, n], sq int64 [NC, n], frames)``."""
-        if self.gpu:
-            self.sync_streams()
-            self.cnt = np.zeros((self.nc, self.n), np.int64)
-            self.sum = np.zeros((self.nc, self.n), np.int64)
-            self.sq = np.zeros((self.nc, self.n), np.int64)
-            for cnt, s, q in self._acc:
-                self.cnt += cnt.cpu().numpy().astype(np.int64)
-                self.sum += s.cpu().numpy()
-                self.sq += q.cpu().numpy()
-        return self.cnt, self.sum, self.sq, self.frames
+        self._add(reference.dark_accumulate_reference(torch.stack([t.reshape(-1) for t in frames]), self.kind,
+                                                      self.adu_lo, self.adu_hi))
 
     def stats(self):
         """The (synchronised) run as a :class:`psana_ray_amd.dark.DarkStats`."""
@@ -904,122 +1073,74 @@ class DarkStatsConsumer(_BatchConsumer):
         return DarkStats(self.spec.name, self.kind, self.adu_lo, self.adu_hi, frames, cnt.copy(), s.copy(), q.copy())
 
 
-class SparseFrameConsumer(_BatchConsumer):
-    """Consumer engine: batches of leased slots -> K-10 zero suppression (csrc/sparse.hip) ->
-    stream-ordered release.
+class _PackedRows(_BatchConsumer):
+    """What the engines with packed per-frame rows share (sparse, droplets): the rows of a batch's
+    frames lie behind each other in the data columns, at most ``cap`` per frame, and reach the host
+    through pinned buffers in two steps per batch -- the header row first, then exactly ``offs[n]``
+    elements of every column.  Finished batches collect in :attr:`results` as the subclass's frame
+    objects (:meth:`take_results` hands them over).  The ring slots are released stream-ordered
+    after the kernels, not after the copies.
 
-    Per frame: the (pixel index, value) pairs with ``thr <= v <= vmax`` (and ``mask != 0``), packed in
-    index order; at most ``cap`` per frame (a frame with more stores nothing and is flagged).  With
-    ``min_peaks > 0`` the peak finder (K-07) runs first on the same stream and its per-frame counts
-    decide ON THE DEVICE which frames are looked at -- no host round trip.  Results reach the host
-    through pinned buffers in two steps per batch: the header (nnz, flags, offs) first, then exactly
-    ``offs[F]`` elements of pix and val; the wait for a batch's header happens after the NEXT batch
-    (on the other stream) has been issued.  Finished batches collect in :attr:`results` as
-    :class:`psana_ray_amd.sparse.SparseFrames` (``take_results`` hands them over).  Ring slots are
-    released stream-ordered after the scan, not after the copies."""
+    The ordering the drain keeps, stated here once:
+      * a batch's header is waited for only when at least ``keep`` newer batches have been issued
+        (``keep = 1`` while polling: after the NEXT batch, on the other stream, is in flight);
+      * its data copy is issued on the batch's OWN stream -- behind the kernels that wrote the rows,
+        ahead of the launch that reuses them (:meth:`_next`) -- for exactly ``offs[n]`` elements,
+        never the full capacity;
+      * it is collected one step later, when another batch is behind it;
+      * :meth:`synchronize` flushes with two ``keep = 0`` passes: the first issues the last data
+        copies, the second collects them.
 
-    name = "sparse"
+    A subclass states ``_HDR``, the per-frame header fields ``(name, dtype name)`` -- header row b is
+    ``offs`` int64 [B + 1], then every field [B], padded to 16 B -- and ``_COLS``, the data columns,
+    sets ``cap`` and calls :meth:`_build_rows` once its batch is final."""
+
     wants_meta = True
+    meta_fields = 4
+    _HDR = ()
+    _COLS = ()
 
-    def __init__(self, endpoint: QueueEndpoint, frame_shape, thr: Optional[float] = None, vmax: Optional[float] = None,
-                 cap: Optional[int] = None, mask=None, min_peaks: int = 0, peak_params: Optional[PeakFinderParams] = None,
-                 detector: str = "", layout: str = "calib", batch: Optional[int] = None,
-                 stream_kind: str = CONSUMER_STREAM_KIND, streams: int = CONSUMER_STREAMS,
-                 ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
-        """frame_shape: the shape of a (calibrated) frame.  check_ring=False: the queue carries RAW
-        frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
-        from . import sparse as _sparse
-        from .ops.reference import validate_sparse_params
-
+    def __init__(self, endpoint: QueueEndpoint, batch: Optional[int], ranks_per_gpu: Optional[int], streams: int,
+                 stream_kind: str):
         super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
-        self.shape = tuple(int(s) for s in frame_shape)
-        self.n = int(np.prod(self.shape))
-        if not 1 <= self.n < 2 ** 31:
-            raise ValueError("sparse: frames must have 1 .. 2^31 - 1 elements")
-        self.thr, self.vmax, self.cap = validate_sparse_params(
-            _sparse.DEFAULT_THR if thr is None else thr, _sparse.DEFAULT_VMAX if vmax is None else vmax,
-            _sparse.default_cap(self.n) if cap is None else cap, self.batch, "sparse")
-        self.min_peaks = int(min_peaks)
-        if self.min_peaks < 0:
-            raise ValueError("sparse: min_peaks must be >= 0")
-        self.peak_params = peak_params or PeakFinderParams()
-        if self.min_peaks > 0:
-            if len(self.shape) not in (2, 3):
-                raise ValueError(f"sparse: the hit filter needs 2-D or 3-D frames, got {self.shape}")
-            if self.peak_params.radius not in (1, 2):
-                raise ValueError("sparse: peak finder radius must be 1 or 2")
-            self._pf_shape = self.shape if len(self.shape) == 3 else (1, *self.shape)
-        self.detector, self.layout = str(detector), str(layout)
-        if check_ring:
-            if endpoint.ring.dtype != torch.float32:
-                raise ValueError(f"sparse: the queue carries {endpoint.ring.dtype} frames, zero suppression needs "
-                                 "calibrated float32 ones")
-            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
-                raise ValueError(f"sparse: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
-        self._mask_np = None
-        if mask is not None:
-            m = np.asarray(mask)
-            if m.dtype != np.uint8 or m.size != self.n or (m.ndim > 1 and tuple(m.shape) != self.shape):
-                raise ValueError(f"sparse: the mask must be uint8 of the frame's shape {self.shape}, got {m.dtype} "
-                                 f"{tuple(m.shape)}")
-            self._mask_np = np.ascontiguousarray(m.reshape(-1))
-        self.frames_stored = self.frames_skipped = self.frames_overflowed = self.pixels_stored = 0
-        self.results = []      # finished batches (SparseFrames), oldest first
+        self.results = []      # finished batches (frame objects), oldest first
         self._pending = collections.deque()   # GPU batches in flight: dicts, oldest first
         self._lock = threading.Lock()
-        if self.gpu:
-            B, dev = self.batch, self.device
-            # header of a batch in ONE row: offs int64 [B + 1] | nnz int32 [B] | flags uint8 [B]
-            self._hdr_bytes = 8 * (B + 1) + 4 * B + B
-            self._hdr = torch.zeros((self._nbuf, (self._hdr_bytes + 15) // 16 * 16), dtype=torch.uint8, device=dev)
-            self._hdr_host = torch.zeros(self._hdr.shape, dtype=torch.uint8, pin_memory=True)
-            self._pix = torch.empty((self._nbuf, B * self.cap), dtype=torch.int32, device=dev)
-            self._val = torch.empty((self._nbuf, B * self.cap), dtype=torch.float32, device=dev)
-            # one scratch block per stream (a block must never serve two launches in flight)
-            self._scratch = [torch.empty(kernels.sparsify_scratch_bytes(self.n, self.cap, B), dtype=torch.uint8, device=dev)
-                             for _ in self.streams]
-            self._mask = None if self._mask_np is None else torch.from_numpy(self._mask_np).to(dev)
-            self._pf = None   # the hit filter's peak finder
-            if self.min_peaks > 0:
-                self._pf = _PeakBuffers(dev, self.peak_params, self._pf_shape, B, self._nbuf, len(self.streams))
 
-    # ------------------------------------------------------------------ buffers
-    def _views(self, b: int, n: int):
-        """(offs [n + 1], nnz [n], flags [n]) views of header row b on the device."""
-        B = self.batch
-        row = self._hdr[b]
-        return (row[:8 * (B + 1)].view(torch.int64)[:n + 1], row[8 * (B + 1):8 * (B + 1) + 4 * B].view(torch.int32)[:n],
-                row[8 * (B + 1) + 4 * B:self._hdr_bytes][:n])
+    def _build_rows(self, scratch_bytes: int):
+        """GPU: the header rows, the data columns ``_out[name]`` [_nbuf, B * cap] and one scratch block
+        per stream (a block must never serve two launches in flight)."""
+        B, dev = self.batch, self.device
+        self._layout, o = [], 0   # (field, dtype name, first byte, byte past its end) of a header row
+        for name, dt in (("offs", "int64"),) + self._HDR:
+            size = np.dtype(dt).itemsize * (B + (name == "offs"))
+            self._layout.append((name, dt, o, o + size))
+            o += size
+        self._hdr_bytes = o
+        self._hdr = torch.zeros((self._nbuf, (o + 15) // 16 * 16), dtype=torch.uint8, device=dev)
+        self._hdr_host = torch.zeros(self._hdr.shape, dtype=torch.uint8, pin_memory=True)
+        self._out = {k: torch.empty((self._nbuf, B * self.cap), dtype=getattr(torch, dt), device=dev)
+                     for k, dt in self._COLS}
+        self._scratch = [torch.empty(scratch_bytes, dtype=torch.uint8, device=dev) for _ in self.streams]
 
-    def _sparse_frames(self, meta, nnz, flags, offs, pix, val):
-        from .sparse import SparseFrames
-
-        return SparseFrames(self.detector, self.layout, self.shape, self.thr, self.vmax, self.cap, self.min_peaks,
-                            self._peak_dict(), rank=[m[0] for m in meta], idx=[m[1] for m in meta],
-                            gevt=[m[2] for m in meta],
-                            photon_energy=[float("nan") if m[3] is None else float(m[3]) for m in meta],
-                            nnz=nnz, flags=flags, offs=offs, pix=pix, val=val)
+    def _split(self, row, n: int) -> dict:
+        """``{"offs": [n + 1], field: [n], ...}``: views of a header row (device tensor or numpy array)."""
+        ns = torch if isinstance(row, torch.Tensor) else np
+        out = {}
+        for name, dt, lo, hi in self._layout:
+            v = row[lo:hi]
+            out[name] = (v if dt == "uint8" else v.view(getattr(ns, dt)))[:n + (name == "offs")]
+        return out
 
     def empty(self):
-        """A SparseFrames of no frames with this consumer's parameters (what a run without frames writes)."""
-        return self._sparse_frames([], np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros(1, np.int64),
-                                   np.zeros(0, np.int32), np.zeros(0, np.float32))
+        """The frame object of no frames with this consumer's parameters (what a run without frames writes)."""
+        hdr = {"offs": np.zeros(1, np.int64), **{k: np.zeros(0, dt) for k, dt in self._HDR}}
+        return self._frames_of([], hdr, {k: np.zeros(0, dt) for k, dt in self._COLS})
 
-    def _peak_dict(self) -> dict:
-        if self.min_peaks <= 0:
-            return {}
-        p = self.peak_params
-        return {"thr_peak": float(p.thr_peak), "son_min": float(p.son_min), "radius": float(p.radius)}
-
-    def _count(self, sf):
-        from .sparse import FLAG_OVERFLOW, FLAG_SKIPPED
-
+    def _collect(self, fr):
         with self._lock:
-            self.frames_skipped += int(((sf.flags & FLAG_SKIPPED) != 0).sum())
-            self.frames_overflowed += int(((sf.flags & FLAG_OVERFLOW) != 0).sum())
-            self.frames_stored += int(((sf.flags & (FLAG_SKIPPED | FLAG_OVERFLOW)) == 0).sum())
-            self.pixels_stored += int(sf.offs[-1])
-            self.results.append(sf)
+            self._count(fr)
+            self.results.append(fr)
 
     # ------------------------------------------------------------------ the two host steps of a GPU batch
     def _launched(self, b: int, n: int, st, meta):
@@ -1034,94 +1155,32 @@ class SparseFrameConsumer(_BatchConsumer):
         """Step every batch but the newest ``keep``: a batch whose header is awaited gets its data copy
         issued; a batch whose data copy was issued is collected once at least one newer batch is behind
         it (or on a flush, keep = 0)."""
-        B = self.batch
         for i, p in enumerate(list(self._pending)):
             if len(self._pending) - i <= keep:
                 break
             if p["data"] is None:
                 p["hdr"].synchronize()
-                row = self._hdr_host[p["b"]].numpy()
-                n = p["n"]
-                p["offs"] = row[:8 * (B + 1)].view(np.int64)[:n + 1].copy()
-                p["nnz"] = row[8 * (B + 1):8 * (B + 1) + 4 * B].view(np.int32)[:n].copy()
-                p["flags"] = row[8 * (B + 1) + 4 * B:self._hdr_bytes][:n].copy()
-                total = int(p["offs"][n])
-                p["pix"] = torch.empty(total, dtype=torch.int32, pin_memory=total > 0)
-                p["val"] = torch.empty(total, dtype=torch.float32, pin_memory=total > 0)
+                p["head"] = {k: v.copy() for k, v in self._split(self._hdr_host[p["b"]].numpy(), p["n"]).items()}
+                total = int(p["head"]["offs"][p["n"]])
+                p["cols"] = {k: torch.empty(total, dtype=getattr(torch, dt), pin_memory=total > 0)
+                             for k, dt in self._COLS}
                 ev = torch.cuda.Event()
-                with torch.cuda.stream(p["st"]):   # exactly offs[F] elements, never the full capacity
+                with torch.cuda.stream(p["st"]):   # exactly offs[n] elements, never the full capacity
                     if total:
-                        p["pix"].copy_(self._pix[p["b"], :total], non_blocking=True)
-                        p["val"].copy_(self._val[p["b"], :total], non_blocking=True)
+                        for k, h in p["cols"].items():
+                            h.copy_(self._out[k][p["b"], :total], non_blocking=True)
                     ev.record(p["st"])
                 p["data"] = ev
         while self._pending and self._pending[0]["data"] is not None and len(self._pending) > 2 * keep:
             p = self._pending.popleft()
             p["data"].synchronize()
-            self._count(self._sparse_frames(p["meta"], p["nnz"], p["flags"], p["offs"], p["pix"].numpy().copy(),
-                                            p["val"].numpy().copy()))
-
-    # ------------------------------------------------------------------ processing
-    def process_frames(self, frames, meta):
-        """Sparsify ``frames`` (tensors of n elements on this consumer's device, issued on the current
-        stream) that are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank,
-        idx, gevt, photon_energy)``.  GPU: returns the consumer stream the batch runs on."""
-        return super().process_frames(frames, [tuple(m) + (None,) * (4 - len(m)) for m in meta])
-
-    def _check_batch(self, n):
-        if n > self.batch:
-            raise ValueError(f"sparse: {n} frames in a batch of at most {self.batch}")
-
-    def _meta_of(self, recs):
-        # a slot header carries NaN for "no photon energy", a queue item None
-        return [(r.rank, r.idx, r.gevt, None if r.photon_energy != r.photon_energy else r.photon_energy)
-                for r in recs]
-
-    def _launch_slots(self, C, slots, b, k, st):
-        offs, nnz, flags = self._views(b, len(slots))
-        keys = 0
-        if self._pf is not None:
-            self._pf.launch_slots(C, self.ep, slots, b, k, st)
-            keys = int(self._pf.counts[b].data_ptr())
-        C.sparsify_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.thr, self.vmax, self.cap,
-                         0 if self._mask is None else int(self._mask.data_ptr()), keys, self.min_peaks,
-                         int(nnz.data_ptr()), int(flags.data_ptr()), int(offs.data_ptr()),
-                         int(self._pix[b].data_ptr()), int(self._val[b].data_ptr()),
-                         int(self._scratch[k].data_ptr()), self._scratch[k].numel(), int(st.cuda_stream))
-
-    def _launch_tensors(self, frames, b, k, st):
-        n = len(frames)
-        offs, nnz, flags = self._views(b, n)
-        keys = None
-        if self._pf is not None:
-            self._pf.launch_tensors(frames, b, k, st)
-            keys = self._pf.counts[b, :n]
-        kernels.sparsify([t.reshape(-1) for t in frames], self.thr, self.vmax, self.cap, nnz, flags, offs, self._pix[b],
-                         self._val[b], mask=self._mask, keys=keys, key_min=self.min_peaks, scratch=self._scratch[k],
-                         stream=st)
-
-    def _reference(self, frames, meta):
-        from .ops import reference
-
-        x = torch.stack([t.reshape(-1) for t in frames])
-        keys = None
-        if self.min_peaks > 0:
-            pk, _ = reference.peakfind_reference(x.reshape(len(frames), *self._pf_shape), self.peak_params)
-            keys = torch.tensor([int(p.shape[0]) for p in pk], dtype=torch.int32)
-        nnz, flags, offs, pix, val = reference.sparsify_reference(x, self.thr, self.vmax, self.cap, mask=self._mask_np,
-                                                                  keys=keys, key_min=self.min_peaks)
-        self._count(self._sparse_frames(meta, nnz.numpy(), flags.numpy(), offs.numpy(), pix.numpy(), val.numpy()))
+            self._collect(self._frames_of(p["meta"], p["head"], {k: h.numpy().copy() for k, h in p["cols"].items()}))
 
     def take_results(self) -> list:
         """The finished batches collected so far (oldest first); they are removed from :attr:`results`."""
         with self._lock:
             out, self.results = self.results, []
         return out
-
-    def metrics(self) -> dict:
-        return {"frames_consumed": self.frames, "frames_stored": self.frames_stored,
-                "frames_skipped": self.frames_skipped, "frames_overflowed": self.frames_overflowed,
-                "pixels_stored": self.pixels_stored}
 
     def synchronize(self):
         """Wait for every batch and collect it.  Returns the list of finished batches not taken yet."""
@@ -1131,27 +1190,132 @@ class SparseFrameConsumer(_BatchConsumer):
             self.sync_streams()
         return self.results
 
+    # ------------------------------------------------------------------ what a packed-rows consumer fills in
+    def _frames_of(self, meta, hdr: dict, cols: dict):
+        """The frame object of a batch: its meta tuples, header fields and data columns (host arrays by name)."""
+        raise NotImplementedError
 
-class PowderConsumer(_BatchConsumer):
+    def _count(self, fr):
+        """Add a finished batch to the counters behind :meth:`metrics` (the lock is held)."""
+
+
+class SparseFrameConsumer(_PackedRows):
+    """Consumer engine: batches of leased slots -> K-10 zero suppression (csrc/sparse.hip) ->
+    stream-ordered release.
+
+    Per frame: the (pixel index, value) pairs with ``thr <= v <= vmax`` (and ``mask != 0``), packed in
+    index order; at most ``cap`` per frame (a frame with more stores nothing and is flagged).  With
+    ``min_peaks > 0`` the hit filter (:class:`_HitFilter`) decides on the device which frames are
+    looked at.  The batches reach :attr:`results` as :class:`psana_ray_amd.sparse.SparseFrames` the
+    way :class:`_PackedRows` states."""
+
+    name = "sparse"
+    _HDR = (("nnz", "int32"), ("flags", "uint8"))
+    _COLS = (("pix", "int32"), ("val", "float32"))
+
+    def __init__(self, endpoint: QueueEndpoint, frame_shape, thr: Optional[float] = None, vmax: Optional[float] = None,
+                 cap: Optional[int] = None, mask=None, min_peaks: int = 0, peak_params: Optional[PeakFinderParams] = None,
+                 detector: str = "", layout: str = "calib", batch: Optional[int] = None,
+                 stream_kind: str = CONSUMER_STREAM_KIND, streams: int = CONSUMER_STREAMS,
+                 ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
+        """frame_shape: the shape of a (calibrated) frame.  check_ring=False: the ring holds RAW
+        frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
+        from . import sparse as _sparse
+        from .ops.reference import validate_sparse_params
+
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        self.shape = tuple(int(s) for s in frame_shape)
+        self.n = int(np.prod(self.shape))
+        if not 1 <= self.n < 2 ** 31:
+            raise ValueError("sparse: frames must have 1 .. 2^31 - 1 elements")
+        self.thr, self.vmax, self.cap = validate_sparse_params(
+            _sparse.DEFAULT_THR if thr is None else thr, _sparse.DEFAULT_VMAX if vmax is None else vmax,
+            _sparse.default_cap(self.n) if cap is None else cap, self.batch, "sparse")
+        self._hits = _HitFilter("sparse", self.shape, min_peaks, peak_params)
+        self.min_peaks, self.peak_params = self._hits.min_peaks, self._hits.params
+        self.detector, self.layout = str(detector), str(layout)
+        if check_ring:
+            self._check_ring(endpoint, "zero suppression needs calibrated float32 ones")
+        self._mask_np = None
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.dtype != np.uint8 or m.size != self.n or (m.ndim > 1 and tuple(m.shape) != self.shape):
+                raise ValueError(f"sparse: the mask must be uint8 of the frame's shape {self.shape}, got {m.dtype} "
+                                 f"{tuple(m.shape)}")
+            self._mask_np = np.ascontiguousarray(m.reshape(-1))
+        self.frames_stored = self.frames_skipped = self.frames_overflowed = self.pixels_stored = 0
+        if self.gpu:
+            self._build_rows(kernels.sparsify_scratch_bytes(self.n, self.cap, self.batch))
+            self._mask = None if self._mask_np is None else torch.from_numpy(self._mask_np).to(self.device)
+            self._hits.allocate(self.device, self.batch, self._nbuf, len(self.streams))
+
+    def _frames_of(self, meta, hdr, cols):
+        from .sparse import SparseFrames
+
+        return SparseFrames(self.detector, self.layout, self.shape, self.thr, self.vmax, self.cap, self.min_peaks,
+                            self._hits.peak_dict(), **self._meta_columns(meta), **hdr, **cols)
+
+    def _count(self, sf):
+        from .sparse import FLAG_OVERFLOW, FLAG_SKIPPED
+
+        self.frames_skipped += int(((sf.flags & FLAG_SKIPPED) != 0).sum())
+        self.frames_overflowed += int(((sf.flags & FLAG_OVERFLOW) != 0).sum())
+        self.frames_stored += int(((sf.flags & (FLAG_SKIPPED | FLAG_OVERFLOW)) == 0).sum())
+        self.pixels_stored += int(sf.offs[-1])
+
+    def _launch_slots(self, C, slots, b, k, st):
+        h, o = self._split(self._hdr[b], len(slots)), self._out
+        keys = self._hits.keys_slots(C, self.ep, slots, b, k, st)
+        C.sparsify_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.thr, self.vmax, self.cap,
+                         0 if self._mask is None else int(self._mask.data_ptr()), keys, self.min_peaks,
+                         int(h["nnz"].data_ptr()), int(h["flags"].data_ptr()), int(h["offs"].data_ptr()),
+                         int(o["pix"][b].data_ptr()), int(o["val"][b].data_ptr()),
+                         int(self._scratch[k].data_ptr()), self._scratch[k].numel(), int(st.cuda_stream))
+
+    def _launch_tensors(self, frames, b, k, st):
+        h, o = self._split(self._hdr[b], len(frames)), self._out
+        keys = self._hits.keys_tensors(frames, b, k, st)
+        kernels.sparsify([t.reshape(-1) for t in frames], self.thr, self.vmax, self.cap, h["nnz"], h["flags"],
+                         h["offs"], o["pix"][b], o["val"][b], mask=self._mask, keys=keys, key_min=self.min_peaks,
+                         scratch=self._scratch[k], stream=st)
+
+    def _reference(self, frames, meta):
+        from .ops import reference
+
+        x = torch.stack([t.reshape(-1) for t in frames])
+        nnz, flags, offs, pix, val = reference.sparsify_reference(x, self.thr, self.vmax, self.cap, mask=self._mask_np,
+                                                                  keys=self._hits.keys_reference(x),
+                                                                  key_min=self.min_peaks)
+        self._collect(self._frames_of(meta, {"offs": offs.numpy(), "nnz": nnz.numpy(), "flags": flags.numpy()},
+                                      {"pix": pix.numpy(), "val": val.numpy()}))
+
+    def metrics(self) -> dict:
+        return {"frames_consumed": self.frames, "frames_stored": self.frames_stored,
+                "frames_skipped": self.frames_skipped, "frames_overflowed": self.frames_overflowed,
+                "pixels_stored": self.pixels_stored}
+
+
+class PowderConsumer(_RunAccumulator):
     """Consumer engine: batches of leased slots -> K-11 powder statistics (csrc/powder.hip) ->
     stream-ordered release.
 
     Per run: per-pixel, per-class count / sum / sum of squares / maximum / count above ``thr_above`` of
     the quantised calibrated value inside ``[vmin, vmax]`` -- integers, so the result is exact in any
-    frame order.  With ``min_peaks > 0`` the peak finder (K-07) runs first on the same stream and its
-    per-frame counts decide ON THE DEVICE whether a frame is a hit (class 1) or a miss (class 0); with
-    ``min_peaks == 0`` there is one class.  The kernel owns a pixel per launch and uses no atomics, so
-    every consumer stream has its OWN accumulator set; :meth:`synchronize` combines the sets on the
-    host (sums, and the maximum for ``qmax``)."""
+    frame order.  With ``min_peaks > 0`` the hit filter (:class:`_HitFilter`) decides on the device
+    whether a frame is a hit (class 1) or a miss (class 0); with ``min_peaks == 0`` there is one class.
+    One accumulator set per consumer stream (:class:`_RunAccumulator`): :meth:`synchronize` returns the
+    dict of ``frames`` int64 [NC], ``cnt`` / ``sum`` / ``sq`` / ``above`` int64 [NC, n] and ``qmax``
+    int32 [NC, n] (the sets' maximum)."""
 
     name = "powder"
+    bound_text = "max_frames = {} (the int32 count and the int64 sum of squares)"
 
     def __init__(self, endpoint: QueueEndpoint, frame_shape, vmin: Optional[float] = None, vmax: Optional[float] = None,
                  frac_bits: Optional[int] = None, thr_above: Optional[float] = None, min_peaks: int = 0,
                  peak_params: Optional[PeakFinderParams] = None, detector: str = "", layout: str = "calib",
                  batch: Optional[int] = None, stream_kind: str = CONSUMER_STREAM_KIND,
                  streams: int = CONSUMER_STREAMS, ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
-        """frame_shape: the shape of a (calibrated) frame.  check_ring=False: the queue carries RAW
+        """frame_shape: the shape of a (calibrated) frame.  check_ring=False: the ring holds RAW
         frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
         from .ops import reference as _ref
 
@@ -1163,96 +1327,36 @@ class PowderConsumer(_BatchConsumer):
             _ref.POWDER_VMIN if vmin is None else vmin, _ref.POWDER_VMAX if vmax is None else vmax,
             _ref.POWDER_FRAC_BITS if frac_bits is None else frac_bits,
             _ref.POWDER_THR_ABOVE if thr_above is None else thr_above, "powder")
-        self.min_peaks = int(min_peaks)
-        if self.min_peaks < 0:
-            raise ValueError("powder: min_peaks must be >= 0")
+        self._hits = _HitFilter("powder", self.shape, min_peaks, peak_params)
+        self.min_peaks, self.peak_params = self._hits.min_peaks, self._hits.params
         self.nc = 2 if self.min_peaks > 0 else 1
-        self.peak_params = peak_params or PeakFinderParams()
-        if self.min_peaks > 0:
-            if len(self.shape) not in (2, 3):
-                raise ValueError(f"powder: the hit filter needs 2-D or 3-D frames, got {self.shape}")
-            if self.peak_params.radius not in (1, 2):
-                raise ValueError("powder: peak finder radius must be 1 or 2")
-            self._pf_shape = self.shape if len(self.shape) == 3 else (1, *self.shape)
         self.detector, self.layout = str(detector), str(layout)
         if check_ring:
-            if endpoint.ring.dtype != torch.float32:
-                raise ValueError(f"powder: the queue carries {endpoint.ring.dtype} frames, powder statistics need "
-                                 "calibrated float32 ones")
-            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
-                raise ValueError(f"powder: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+            self._check_ring(endpoint, "powder statistics need calibrated float32 ones")
         super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
-        self._host = self._new_host()
         if self.gpu:
-            dev, nc, n = self.device, self.nc, self.n
-            # one accumulator set per stream; set k is only ever touched by launches on stream k
-            self._acc = [(torch.zeros(nc, dtype=torch.int64, device=dev),
-                          torch.zeros((nc, n), dtype=torch.int32, device=dev),
-                          torch.zeros((nc, n), dtype=torch.int64, device=dev),
-                          torch.zeros((nc, n), dtype=torch.int64, device=dev),
-                          torch.full((nc, n), _ref.POWDER_QMAX_NONE, dtype=torch.int32, device=dev),
-                          torch.zeros((nc, n), dtype=torch.int32, device=dev))
-                         for _ in self.streams]
-            self._pf = None   # the hit filter's peak finder
-            if self.min_peaks > 0:
-                self._pf = _PeakBuffers(dev, self.peak_params, self._pf_shape, self.batch, self._nbuf,
-                                        len(self.streams))
+            self._hits.allocate(self.device, self.batch, self._nbuf, len(self.streams))
 
-    def _new_host(self) -> dict:
+    def _fields(self):
         from .ops.reference import POWDER_QMAX_NONE
 
-        nc, n = self.nc, self.n
-        return {"frames": np.zeros(nc, np.int64), "cnt": np.zeros((nc, n), np.int64),
-                "sum": np.zeros((nc, n), np.int64), "sq": np.zeros((nc, n), np.int64),
-                "qmax": np.full((nc, n), POWDER_QMAX_NONE, np.int32), "above": np.zeros((nc, n), np.int64)}
-
-    @staticmethod
-    def _combine(h: dict, nfr, cnt, s, sq, qmax, above):
-        h["frames"] += nfr
-        h["cnt"] += cnt.astype(np.int64)
-        h["sum"] += s
-        h["sq"] += sq
-        h["qmax"] = np.maximum(h["qmax"], qmax)
-        h["above"] += above.astype(np.int64)
-
-    def _check_bound(self, n: int):
-        if self.frames + n > self.max_frames:
-            raise ValueError(f"powder: {self.frames} + {n} frames would take the run past max_frames = "
-                             f"{self.max_frames} (the int32 count and the int64 sum of squares)")
-
-    def _check_batch(self, n):
-        if n > self.batch:
-            raise ValueError(f"powder: {n} frames in a batch of at most {self.batch}")
-        self._check_bound(n)
-
-    def _limit(self, n_max):
-        self._check_bound(1)   # before any lease
-        return max(1, min(n_max, self.max_frames - self.frames))
-
-    def _peak_dict(self) -> dict:
-        if self.min_peaks <= 0:
-            return {}
-        p = self.peak_params
-        return {"thr_peak": float(p.thr_peak), "son_min": float(p.son_min), "radius": float(p.radius)}
+        c, s = (self.nc,), (self.nc, self.n)
+        return (_Field("frames", c, torch.int64, np.int64), _Field("cnt", s, torch.int32, np.int64),
+                _Field("sum", s, torch.int64, np.int64), _Field("sq", s, torch.int64, np.int64),
+                _Field("qmax", s, torch.int32, np.int32, POWDER_QMAX_NONE, "max"),
+                _Field("above", s, torch.int32, np.int64))
 
     def _launch_slots(self, C, slots, b, k, st):
         nfr, cnt, s, q, qmax, above = self._acc[k]
-        keys = 0
-        if self._pf is not None:
-            self._pf.launch_slots(C, self.ep, slots, b, k, st)
-            keys = int(self._pf.counts[b].data_ptr())
+        keys = self._hits.keys_slots(C, self.ep, slots, b, k, st)
         C.powder_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.vmin, self.vmax, self.frac_bits,
                        self.thr_above, self.nc, keys, self.min_peaks, int(nfr.data_ptr()), int(cnt.data_ptr()),
                        int(s.data_ptr()), int(q.data_ptr()), int(qmax.data_ptr()), int(above.data_ptr()),
                        int(st.cuda_stream))
 
     def _launch_tensors(self, frames, b, k, st):
-        n = len(frames)
         nfr, cnt, s, q, qmax, above = self._acc[k]
-        keys = None
-        if self._pf is not None:
-            self._pf.launch_tensors(frames, b, k, st)
-            keys = self._pf.counts[b, :n]
+        keys = self._hits.keys_tensors(frames, b, k, st)
         kernels.powder_accumulate([t.reshape(-1) for t in frames], self.vmin, self.vmax, self.frac_bits,
                                   self.thr_above, nfr, cnt, s, q, qmax, above, keys=keys, key_min=self.min_peaks,
                                   frames_so_far=self.frames, stream=st)
@@ -1261,24 +1365,8 @@ class PowderConsumer(_BatchConsumer):
         from .ops import reference
 
         x = torch.stack([t.reshape(-1) for t in frames])
-        keys = None
-        if self.min_peaks > 0:
-            pk, _ = reference.peakfind_reference(x.reshape(len(frames), *self._pf_shape), self.peak_params)
-            keys = torch.tensor([int(p.shape[0]) for p in pk], dtype=torch.int32)
-        out = reference.powder_accumulate_reference(x, self.vmin, self.vmax, self.frac_bits, self.thr_above,
-                                                    keys=keys, key_min=self.min_peaks)
-        self._combine(self._host, *(t.numpy() for t in out))
-
-    def synchronize(self):
-        """Wait for every batch and combine the per-stream accumulator sets on the host (exact).  Returns
-        the dict of ``frames`` int64 [NC], ``cnt`` / ``sum`` / ``sq`` / ``above`` int64 [NC, n] and
-        ``qmax`` int32 [NC, n]."""
-        if self.gpu:
-            self.sync_streams()
-            self._host = self._new_host()
-            for acc in self._acc:
-                self._combine(self._host, *(t.cpu().numpy() for t in acc))
-        return self._host
+        self._add(reference.powder_accumulate_reference(x, self.vmin, self.vmax, self.frac_bits, self.thr_above,
+                                                        keys=self._hits.keys_reference(x), key_min=self.min_peaks))
 
     def stats(self):
         """The (synchronised) run as a :class:`psana_ray_amd.powder.PowderStats`."""
@@ -1286,26 +1374,26 @@ class PowderConsumer(_BatchConsumer):
 
         h = self.synchronize()
         return PowderStats(self.detector, self.layout, self.shape, self.vmin, self.vmax, self.frac_bits,
-                           self.thr_above, self.min_peaks, self._peak_dict(), h["frames"].copy(), h["cnt"].copy(),
+                           self.thr_above, self.min_peaks, self._hits.peak_dict(), h["frames"].copy(), h["cnt"].copy(),
                            h["sum"].copy(), h["sq"].copy(), h["above"].copy(), h["qmax"].copy())
 
 
-class PixelHistConsumer(_BatchConsumer):
+class PixelHistConsumer(_RunAccumulator):
     """Consumer engine: batches of leased slots -> K-12 per-pixel histograms (csrc/pixhist.hip) ->
     stream-ordered release.
 
     Per run: how often every pixel read a value in each of ``nbins`` equal bins of ``[lo, hi]`` -- integers,
-    so the result is exact in any frame order.  The kernel owns a pixel per launch and uses no global
-    atomics, so every consumer stream has its OWN accumulator int32 ``[n, nbins]``; :meth:`synchronize` adds
-    them on the device and copies one result to the host."""
+    so the result is exact in any frame order.  One accumulator int32 ``[n, nbins]`` per consumer stream
+    (:class:`_RunAccumulator`): :meth:`synchronize` returns their sum, ``hist`` int32 [n, nbins]."""
 
     name = "hist"
+    bound_text = "{} (the int32 count of a bin)"
 
     def __init__(self, endpoint: QueueEndpoint, frame_shape, lo: Optional[float] = None, hi: Optional[float] = None,
                  nbins: Optional[int] = None, detector: str = "", layout: str = "calib", batch: Optional[int] = None,
                  stream_kind: str = CONSUMER_STREAM_KIND, streams: int = CONSUMER_STREAMS,
                  ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
-        """frame_shape: the shape of a (calibrated) frame.  check_ring=False: the queue carries RAW
+        """frame_shape: the shape of a (calibrated) frame.  check_ring=False: the ring holds RAW
         frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
         from .ops import reference as _ref
 
@@ -1317,34 +1405,14 @@ class PixelHistConsumer(_BatchConsumer):
         self.max_frames = _ref.HIST_MAX_FRAMES
         self.detector, self.layout = str(detector), str(layout)
         if check_ring:
-            if endpoint.ring.dtype != torch.float32:
-                raise ValueError(f"hist: the queue carries {endpoint.ring.dtype} frames, pixel histograms need "
-                                 "calibrated float32 ones")
-            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
-                raise ValueError(f"hist: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+            self._check_ring(endpoint, "pixel histograms need calibrated float32 ones")
         super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
-        self._host = np.zeros((self.n, self.nbins), np.int32)
         self.acc_bytes = self.n * self.nbins * 4 * max(1, len(self.streams))
         log.info("hist: %d accumulator(s) of %d x %d int32 = %.1f MB in all", max(1, len(self.streams)), self.n,
                  self.nbins, self.acc_bytes / 1e6)
-        if self.gpu:
-            # one accumulator per stream; accumulator k is only ever touched by launches on stream k
-            self._acc = [torch.zeros((self.n, self.nbins), dtype=torch.int32, device=self.device)
-                         for _ in self.streams]
 
-    def _check_bound(self, n: int):
-        if self.frames + n > self.max_frames:
-            raise ValueError(f"hist: {self.frames} + {n} frames would take the run past {self.max_frames} "
-                             "(the int32 count of a bin)")
-
-    def _check_batch(self, n):
-        if n > self.batch:
-            raise ValueError(f"hist: {n} frames in a batch of at most {self.batch}")
-        self._check_bound(n)
-
-    def _limit(self, n_max):
-        self._check_bound(1)   # before any lease
-        return max(1, min(n_max, self.max_frames - self.frames))
+    def _fields(self):
+        return (_Field("hist", (self.n, self.nbins), torch.int32, np.int32),)
 
     def _launch_slots(self, C, slots, b, k, st):
         C.pixel_hist_slots(self.ep.pool, self.ep._slot_bytes, slots, self.n, self.lo, self.hi, self.inv_w, self.nbins,
@@ -1358,23 +1426,7 @@ class PixelHistConsumer(_BatchConsumer):
         from .ops import reference
 
         x = torch.stack([t.reshape(-1) for t in frames])
-        self._host += reference.pixel_hist_reference(x, self.lo, self.hi, self.nbins).numpy()
-
-    def synchronize(self) -> np.ndarray:
-        """Wait for every batch, add the per-stream accumulators ON THE DEVICE (exact; a bin of the run is at
-        most its frames, which the bound keeps inside an int32) and copy the one result to the host.
-        Returns ``hist`` int32 [n, nbins]."""
-        if self.gpu:
-            self.sync_streams()
-            with torch.cuda.device(self.device):
-                total = self._acc[0]
-                if len(self._acc) > 1:
-                    total = self._acc[0].clone()
-                    for a in self._acc[1:]:
-                        total += a
-                self._host = total.cpu().numpy()
-                del total
-        return self._host
+        self._add((reference.pixel_hist_reference(x, self.lo, self.hi, self.nbins),))
 
     def stats(self):
         """The (synchronised) run as a :class:`psana_ray_amd.hist.PixelHist`."""
@@ -1384,19 +1436,21 @@ class PixelHistConsumer(_BatchConsumer):
                          self.synchronize().copy())
 
 
-class PhotonConsumer(_BatchConsumer):
+class PhotonConsumer(_RunAccumulator):
     """Consumer engine: batches of leased slots -> K-13 photon counting (csrc/photons.hip) ->
     stream-ordered release.
 
     Per run: per pixel the samples (``cnt``), the photons (``psum``) and the frames with at least one photon
     (``occ``); per frame and ROI the photon-count distribution ``pk`` [R, 8] and the photons ``tot`` [R] --
     integers, so the result is exact in any frame order.  The frames never leave the GPU: the per-frame rows
-    (a few hundred bytes) go to pinned host memory stream-ordered.  The kernel owns a pixel per launch and
-    uses no global atomics on the run accumulators, so every consumer stream has its OWN set;
-    :meth:`synchronize` adds the sets on the device and copies one result to the host."""
+    (a few hundred bytes) go to pinned host memory stream-ordered.  One set of run maps per consumer stream
+    (:class:`_RunAccumulator`): :meth:`synchronize` returns the dict of ``cnt`` int32 / ``psum`` int64 /
+    ``occ`` int32 [n]."""
 
     name = "photons"
     wants_meta = True
+    meta_fields = 4
+    bound_text = "{} (the int32 counts of a pixel)"
 
     def __init__(self, endpoint: QueueEndpoint, frame_shape, adu_per_photon, vmax: Optional[float] = None,
                  thr_seed: Optional[float] = None, thr_total: Optional[float] = None, mask=None, roi=None,
@@ -1405,7 +1459,7 @@ class PhotonConsumer(_BatchConsumer):
                  ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
         """frame_shape: the shape of a (calibrated) frame, [P, H, W] or [H, W].  mask / roi: uint8 arrays of
         that many elements (keep-mask; ROI labels 0 .. R - 1, 255 = none), or None.  check_ring=False: the
-        queue carries RAW frames that the caller calibrates before :meth:`process_frames`
+        ring holds RAW frames that the caller calibrates before :meth:`process_frames`
         (``--calibrate_on_read``)."""
         from .ops import reference as _ref
 
@@ -1417,21 +1471,13 @@ class PhotonConsumer(_BatchConsumer):
         self.max_frames = _ref.PHOTON_MAX_FRAMES
         self.detector, self.layout = str(detector), str(layout)
         if check_ring:
-            if endpoint.ring.dtype != torch.float32:
-                raise ValueError(f"photons: the queue carries {endpoint.ring.dtype} frames, photon counting needs "
-                                 "calibrated float32 ones")
-            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
-                raise ValueError(f"photons: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+            self._check_ring(endpoint, "photon counting needs calibrated float32 ones")
         super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
-        self._host = self._new_host()
         # per batch: (pk int32 [n, R, 8], tot int64 [n, R], [(rank, idx, gevt, photon_energy), ...]); on the GPU
         # path the arrays are pinned host tensors filled asynchronously: valid after sync_streams()
         self.results = []
         if self.gpu:
             dev, n, B, R = self.device, self.n, self.batch, self.n_roi
-            # one accumulator set per stream; set k is only ever touched by launches on stream k
-            self._acc = [(torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
-                          torch.zeros(n, dtype=torch.int32, device=dev)) for _ in self.streams]
             self._pk = torch.zeros((self._nbuf, B, R, _ref.PHOTON_PK_BINS), dtype=torch.int32, device=dev)
             self._tot = torch.zeros((self._nbuf, B, R), dtype=torch.int64, device=dev)
             self._mask = None if self._mask_np is None else torch.from_numpy(self._mask_np).to(dev)
@@ -1439,34 +1485,10 @@ class PhotonConsumer(_BatchConsumer):
             if self._roi is not None:
                 self._roi._pr_checked_roi = (n, R)   # validated on the host above
 
-    def _new_host(self) -> dict:
-        n = self.n
-        return {"cnt": np.zeros(n, np.int32), "psum": np.zeros(n, np.int64), "occ": np.zeros(n, np.int32)}
-
-    def _check_bound(self, n: int):
-        if self.frames + n > self.max_frames:
-            raise ValueError(f"photons: {self.frames} + {n} frames would take the run past {self.max_frames} "
-                             "(the int32 counts of a pixel)")
-
-    def _check_batch(self, n):
-        if n > self.batch:
-            raise ValueError(f"photons: {n} frames in a batch of at most {self.batch}")
-        self._check_bound(n)
-
-    def _limit(self, n_max):
-        self._check_bound(1)   # before any lease
-        return max(1, min(n_max, self.max_frames - self.frames))
-
-    def process_frames(self, frames, meta):
-        """Count ``frames`` (tensors of n elements on this consumer's device, issued on the current stream)
-        that are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank, idx, gevt,
-        photon_energy)``.  GPU: returns the consumer stream the batch runs on."""
-        return super().process_frames(frames, [tuple(m) + (None,) * (4 - len(m)) for m in meta])
-
-    def _meta_of(self, recs):
-        # a slot header carries NaN for "no photon energy", a queue item None
-        return [(r.rank, r.idx, r.gevt, None if r.photon_energy != r.photon_energy else r.photon_energy)
-                for r in recs]
+    def _fields(self):
+        s = (self.n,)
+        return (_Field("cnt", s, torch.int32, np.int32), _Field("psum", s, torch.int64, np.int64),
+                _Field("occ", s, torch.int32, np.int32))
 
     def _launch_slots(self, C, slots, b, k, st):
         P, H, W = self.phw
@@ -1486,60 +1508,27 @@ class PhotonConsumer(_BatchConsumer):
                         frames_so_far=self.frames, stream=st)
 
     def _launched(self, b, n, st, meta):
-        """The batch's per-frame rows go to PINNED HOST memory by asynchronous copies on the current
-        (consumer) stream; the kept tensors are valid after :meth:`sync_streams`."""
-        from .ops.reference import PHOTON_PK_BINS
-
-        pk = torch.empty((n, self.n_roi, PHOTON_PK_BINS), dtype=torch.int32, pin_memory=True)
-        tot = torch.empty((n, self.n_roi), dtype=torch.int64, pin_memory=True)
-        pk.copy_(self._pk[b, :n], non_blocking=True)
-        tot.copy_(self._tot[b, :n], non_blocking=True)
-        self.results.append((pk, tot, meta))
+        self._keep_pinned((self._pk, self._tot), b, n, meta)
 
     def _reference(self, frames, meta):
         from .ops import reference
 
         x = torch.stack([t.reshape(-1) for t in frames])
         out = reference.photon_count_reference(x, self.phw, self.params, self._mask_np, self._roi_np, self.n_roi)
-        self._host["cnt"] += out.cnt.numpy()
-        self._host["psum"] += out.psum.numpy()
-        self._host["occ"] += out.occ.numpy()
+        self._add((out.cnt, out.psum, out.occ))
         self.results.append((out.pk, out.tot, list(meta)))
-
-    def synchronize(self) -> dict:
-        """Wait for every batch, add the per-stream accumulator sets ON THE DEVICE (exact: a count of the run
-        is at most its frames, which the bound keeps inside an int32) and copy the one result to the host.
-        Returns the dict of ``cnt`` int32 / ``psum`` int64 / ``occ`` int32 [n]."""
-        if self.gpu:
-            self.sync_streams()
-            with torch.cuda.device(self.device):
-                host = {}
-                for i, name in enumerate(("cnt", "psum", "occ")):
-                    total = self._acc[0][i]
-                    if len(self._acc) > 1:
-                        total = total.clone()
-                        for acc in self._acc[1:]:
-                            total += acc[i]
-                    host[name] = total.cpu().numpy()
-                    del total
-                self._host = host
-        return self._host
 
     def stats(self):
         """The (synchronised) run as a :class:`psana_ray_amd.photons.PhotonStats`."""
         from .photons import PhotonStats
 
         h = self.synchronize()
-        meta = [m for _, _, ms in self.results for m in ms]
-        as_np = lambda t: t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)   # noqa: E731
         R = self.n_roi
-        pk = np.concatenate([as_np(p) for p, _, _ in self.results]) if self.results else np.zeros((0, R, 8), np.int32)
-        tot = np.concatenate([as_np(t) for _, t, _ in self.results]) if self.results else np.zeros((0, R), np.int64)
         return PhotonStats.from_maps(self.detector, self.layout, self.shape, self.params, self._mask_np, self._roi_np,
                                      R, self.frames, h["cnt"].copy(), h["psum"].copy(), h["occ"].copy(),
-                                     rank=[m[0] for m in meta], idx=[m[1] for m in meta], gevt=[m[2] for m in meta],
-                                     photon_energy=[float("nan") if m[3] is None else float(m[3]) for m in meta],
-                                     pk=pk.copy(), tot=tot.copy())
+                                     **self._meta_columns([m for *_, ms in self.results for m in ms]),
+                                     pk=self._cat([r[0] for r in self.results], np.zeros((0, R, 8), np.int32)),
+                                     tot=self._cat([r[1] for r in self.results], np.zeros((0, R), np.int64)))
 
 
 class RoiConsumer(_BatchConsumer):
@@ -1553,6 +1542,7 @@ class RoiConsumer(_BatchConsumer):
 
     name = "roi"
     wants_meta = True
+    meta_fields = 4
 
     def __init__(self, endpoint: QueueEndpoint, frame_shape, rects, vmin: Optional[float] = None,
                  vmax: Optional[float] = None, frac_bits: Optional[int] = None, proj: str = "none", mask=None,
@@ -1561,8 +1551,8 @@ class RoiConsumer(_BatchConsumer):
                  ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
         """frame_shape: the shape of a (calibrated) frame, [P, H, W] or [H, W].  rects: a
         :class:`psana_ray_amd.roi.RoiSet`, or int rows (p, y0, y1, x0, x1) -- (y0, y1, x0, x1) for 2-D frames.
-        mask: a uint8 array of a frame's elements (non-zero = keep), or None.  check_ring=False: the queue
-        carries RAW frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
+        mask: a uint8 array of a frame's elements (non-zero = keep), or None.  check_ring=False: the ring
+        holds RAW frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
         from .ops import reference as _ref
         from .roi import RoiSet, mask_sha256
 
@@ -1586,11 +1576,7 @@ class RoiConsumer(_BatchConsumer):
         self.row_bytes = self.roiset.row_bytes(self.proj)
         self.detector, self.layout = str(detector), str(layout)
         if check_ring:
-            if endpoint.ring.dtype != torch.float32:
-                raise ValueError(f"roi: the queue carries {endpoint.ring.dtype} frames, ROI statistics need "
-                                 "calibrated float32 ones")
-            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
-                raise ValueError(f"roi: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+            self._check_ring(endpoint, "ROI statistics need calibrated float32 ones")
         super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
         # per batch: (rows int64 [n, R, 8], proj_x int64 [n, Lx], proj_y int64 [n, Ly], [(rank, idx, gevt,
         # photon_energy), ...]); on the GPU path the arrays are pinned host tensors filled asynchronously: valid
@@ -1603,21 +1589,6 @@ class RoiConsumer(_BatchConsumer):
             self._py = torch.zeros((self._nbuf, B, self.Ly), dtype=torch.int64, device=dev) if self._want_y else None
             self._mask = None if self._mask_np is None else torch.from_numpy(self._mask_np).to(dev)
             self._plan = kernels.roi_plan(self.phw, self.rects, dev)
-
-    def _check_batch(self, n):
-        if n > self.batch:
-            raise ValueError(f"roi: {n} frames in a batch of at most {self.batch}")
-
-    def process_frames(self, frames, meta):
-        """Process ``frames`` (tensors of n elements on this consumer's device, issued on the current stream)
-        that are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank, idx, gevt,
-        photon_energy)``.  GPU: returns the consumer stream the batch runs on."""
-        return super().process_frames(frames, [tuple(m) + (None,) * (4 - len(m)) for m in meta])
-
-    def _meta_of(self, recs):
-        # a slot header carries NaN for "no photon energy", a queue item None
-        return [(r.rank, r.idx, r.gevt, None if r.photon_energy != r.photon_energy else r.photon_energy)
-                for r in recs]
 
     def _launch_slots(self, C, slots, b, k, st):
         C.roi_slots(self.ep.pool, self.ep._slot_bytes, slots, self._plan, self.vmin, self.vmax, self.frac_bits,
@@ -1632,20 +1603,7 @@ class RoiConsumer(_BatchConsumer):
                           None if self._py is None else self._py[b, :n], mask=self._mask, stream=st)
 
     def _launched(self, b, n, st, meta):
-        """The batch's per-frame rows go to PINNED HOST memory by asynchronous copies on the current
-        (consumer) stream; the kept tensors are valid after :meth:`sync_streams`."""
-        from .ops.reference import ROI_ROW_WORDS
-
-        rows = torch.empty((n, self.n_roi, ROI_ROW_WORDS), dtype=torch.int64, pin_memory=True)
-        rows.copy_(self._rows[b, :n], non_blocking=True)
-        px = py = None
-        if self._px is not None:
-            px = torch.empty((n, self.Lx), dtype=torch.int64, pin_memory=True)
-            px.copy_(self._px[b, :n], non_blocking=True)
-        if self._py is not None:
-            py = torch.empty((n, self.Ly), dtype=torch.int64, pin_memory=True)
-            py.copy_(self._py[b, :n], non_blocking=True)
-        self.results.append((rows, px, py, meta))
+        self._keep_pinned((self._rows, self._px, self._py), b, n, meta)
 
     def _reference(self, frames, meta):
         from .ops import reference
@@ -1667,37 +1625,29 @@ class RoiConsumer(_BatchConsumer):
         from .roi import RoiFrames
 
         self.synchronize()
-        meta = [m for *_, ms in self.results for m in ms]
-        as_np = lambda t: t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)   # noqa: E731
-
-        def cat(i):   # None: nothing kept (an axis not selected, or no batch yet) -> RoiFrames makes it empty
-            parts = [as_np(r[i]) for r in self.results if r[i] is not None]
-            return np.concatenate(parts).copy() if parts else None
-
-        rows = cat(0) if self.results else np.zeros((0, self.n_roi, ROI_ROW_WORDS), np.int64)
+        rows = self._cat([r[0] for r in self.results], np.zeros((0, self.n_roi, ROI_ROW_WORDS), np.int64))
+        # None: nothing kept (an axis not selected, or no batch yet) -> RoiFrames makes it empty
+        px, py = self._cat([r[1] for r in self.results]), self._cat([r[2] for r in self.results])
         return RoiFrames.from_rows(self.detector, self.layout, self.shape, self.vmin, self.vmax, self.frac_bits,
-                                   self.proj, self.rects, self.mask_sha256, rows, cat(1), cat(2),
-                                   rank=[m[0] for m in meta], idx=[m[1] for m in meta], gevt=[m[2] for m in meta],
-                                   photon_energy=[float("nan") if m[3] is None else float(m[3]) for m in meta])
+                                   self.proj, self.rects, self.mask_sha256, rows, px, py,
+                                   **self._meta_columns([m for *_, ms in self.results for m in ms]))
 
 
-class DropletConsumer(_BatchConsumer):
+class DropletConsumer(_PackedRows):
     """Consumer engine: batches of leased slots -> K-14 droplets (csrc/droplets.hip) -> stream-ordered release.
 
     Per frame: the 4-connected clusters of pixels with ``thr_low <= v <= vmax`` (and ``mask != 0``) that hold a
     pixel ``v >= thr_seed``, each as integers (label, npix, adu, sy, sx, qmax), label ascending; at most
     ``pix_cap`` active pixels and ``cap`` droplets per frame (a frame with more stores nothing and is flagged).
-    Results reach the host through pinned buffers in two steps per batch, as SparseFrameConsumer's do: the
-    header (offs, nact, ndrop, flags) first, then exactly ``offs[F]`` rows of the six columns; the wait for a
-    batch's header happens after the NEXT batch (on the other stream) has been issued.  Finished batches collect
-    in :attr:`results` as :class:`psana_ray_amd.droplets.DropletFrames`.  Only the first launch of a batch (K-10's
-    scan) reads frame values, so the ring slots go back stream-ordered right after the native call.  One scratch
-    block and one output set per stream; a batch that would not fit the free HBM share is lowered, not refused."""
+    The batches reach :attr:`results` as :class:`psana_ray_amd.droplets.DropletFrames` the way
+    :class:`_PackedRows` states.  Only the first launch of a batch (K-10's scan) reads frame values, so the
+    ring slots go back stream-ordered right after the native call.  A batch that would not fit the free HBM
+    share is lowered, not refused."""
 
     name = "droplets"
-    wants_meta = True
-    _COLS = (("label", torch.int32), ("npix", torch.int32), ("adu", torch.int64), ("sy", torch.int64),
-             ("sx", torch.int64), ("qmax", torch.int32))
+    _HDR = (("nact", "int32"), ("ndrop", "int32"), ("flags", "uint8"))
+    _COLS = (("label", "int32"), ("npix", "int32"), ("adu", "int64"), ("sy", "int64"), ("sx", "int64"),
+             ("qmax", "int32"))
 
     def __init__(self, endpoint: QueueEndpoint, frame_shape, thr_low, thr_seed: Optional[float] = None,
                  vmax: Optional[float] = None, frac_bits: Optional[int] = None, pix_cap: Optional[int] = None,
@@ -1705,7 +1655,7 @@ class DropletConsumer(_BatchConsumer):
                  batch: Optional[int] = None, stream_kind: str = CONSUMER_STREAM_KIND, streams: int = CONSUMER_STREAMS,
                  ranks_per_gpu: Optional[int] = None, check_ring: bool = True, hbm_budget: Optional[int] = None):
         """frame_shape: the shape of a (calibrated) frame, [P, H, W] or [H, W].  mask: uint8 keep-mask of that many
-        elements, or None.  check_ring=False: the queue carries RAW frames that the caller calibrates before
+        elements, or None.  check_ring=False: the ring holds RAW frames that the caller calibrates before
         :meth:`process_frames` (``--calibrate_on_read``).  hbm_budget: bytes this consumer's scratch blocks and
         outputs may take (None: half of the free device memory divided by the ranks sharing the GPU)."""
         from . import droplets as _dr
@@ -1719,17 +1669,10 @@ class DropletConsumer(_BatchConsumer):
         self.mask_sha256 = _dr.mask_hash(self.phw, self._mask_np)
         self.detector, self.layout = str(detector), str(layout)
         if check_ring:
-            if endpoint.ring.dtype != torch.float32:
-                raise ValueError(f"droplets: the queue carries {endpoint.ring.dtype} frames, droplets need "
-                                 "calibrated float32 ones")
-            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
-                raise ValueError(f"droplets: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+            self._check_ring(endpoint, "droplets need calibrated float32 ones")
         super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
         self.pix_cap, self.cap = _ref.validate_droplet_caps(self.phw, self.params, pix_cap, cap, self.batch, "droplets")
         self.frames_stored = self.frames_overflowed = self.droplets_stored = 0
-        self.results = []      # finished batches (DropletFrames), oldest first
-        self._pending = collections.deque()   # GPU batches in flight: dicts, oldest first
-        self._lock = threading.Lock()
         self.scratch_bytes = 0
         if self.gpu:
             dev, ns = self.device, len(self.streams)
@@ -1754,99 +1697,24 @@ class DropletConsumer(_BatchConsumer):
             self.scratch_bytes = kernels.droplets_scratch_bytes(self.n, self.pix_cap, self.cap, B)
             log.info("droplets: %d scratch block(s) of %.1f MB (52 B per row of %d x %d active pixels), outputs %.1f MB",
                      ns, self.scratch_bytes / 1e6, B, self.pix_cap, self._nbuf * B * self.cap * 36 / 1e6)
-            # header of a batch in ONE row: offs int64 [B + 1] | nact int32 [B] | ndrop int32 [B] | flags uint8 [B]
-            self._hdr_bytes = 8 * (B + 1) + 9 * B
-            self._hdr = torch.zeros((self._nbuf, (self._hdr_bytes + 15) // 16 * 16), dtype=torch.uint8, device=dev)
-            self._hdr_host = torch.zeros(self._hdr.shape, dtype=torch.uint8, pin_memory=True)
-            self._out = {k: torch.empty((self._nbuf, B * self.cap), dtype=dt, device=dev) for k, dt in self._COLS}
-            # one scratch block per stream (a block must never serve two launches in flight)
-            self._scratch = [torch.empty(self.scratch_bytes, dtype=torch.uint8, device=dev) for _ in self.streams]
+            self._build_rows(self.scratch_bytes)
             self._mask = None if self._mask_np is None else torch.from_numpy(self._mask_np).to(dev)
 
-    # ------------------------------------------------------------------ buffers
-    def _split(self, row, n: int):
-        """(offs [n + 1], nact [n], ndrop [n], flags [n]) views of a header row (device tensor or numpy)."""
-        B = self.batch
-        i64, i32 = (torch.int64, torch.int32) if isinstance(row, torch.Tensor) else (np.int64, np.int32)
-        o = 8 * (B + 1)
-        return (row[:o].view(i64)[:n + 1], row[o:o + 4 * B].view(i32)[:n], row[o + 4 * B:o + 8 * B].view(i32)[:n],
-                row[o + 8 * B:self._hdr_bytes][:n])
-
-    def _droplet_frames(self, meta, nact, ndrop, flags, offs, cols):
+    def _frames_of(self, meta, hdr, cols):
         from .droplets import DropletFrames
 
         return DropletFrames(self.detector, self.layout, self.phw, self.params.thr_low, self.params.thr_seed,
                              self.params.vmax, self.params.frac_bits, self.pix_cap, self.cap, self.mask_sha256,
-                             rank=[m[0] for m in meta], idx=[m[1] for m in meta], gevt=[m[2] for m in meta],
-                             photon_energy=[float("nan") if m[3] is None else float(m[3]) for m in meta],
-                             nact=nact, ndrop=ndrop, flags=flags, offs=offs, **cols)
-
-    def empty(self):
-        """A DropletFrames of no frames with this consumer's parameters (what a run without frames writes)."""
-        return self._droplet_frames([], np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8),
-                                    np.zeros(1, np.int64), {k: np.zeros(0) for k, _ in self._COLS})
+                             **self._meta_columns(meta), **hdr, **cols)
 
     def _count(self, df):
         over = int((df.flags != 0).sum())
-        with self._lock:
-            self.frames_overflowed += over
-            self.frames_stored += len(df) - over
-            self.droplets_stored += int(df.offs[-1])
-            self.results.append(df)
-
-    # ------------------------------------------------------------------ the two host steps of a GPU batch
-    def _launched(self, b: int, n: int, st, meta):
-        """Batch just launched on ``st`` (current stream): header -> pinned host, then advance the older batches."""
-        self._hdr_host[b].copy_(self._hdr[b], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(st)
-        self._pending.append({"b": b, "n": n, "st": st, "meta": meta, "hdr": ev, "data": None})
-        self._advance(keep=1)
-
-    def _advance(self, keep: int):
-        """Step every batch but the newest ``keep``: a batch whose header is awaited gets its data copy issued; a
-        batch whose data copy was issued is collected once at least one newer batch is behind it (or on a
-        flush, keep = 0)."""
-        for i, p in enumerate(list(self._pending)):
-            if len(self._pending) - i <= keep:
-                break
-            if p["data"] is None:
-                p["hdr"].synchronize()
-                offs, nact, ndrop, flags = self._split(self._hdr_host[p["b"]].numpy(), p["n"])
-                p["offs"], p["nact"], p["ndrop"], p["flags"] = offs.copy(), nact.copy(), ndrop.copy(), flags.copy()
-                total = int(p["offs"][p["n"]])
-                p["cols"] = {k: torch.empty(total, dtype=dt, pin_memory=total > 0) for k, dt in self._COLS}
-                ev = torch.cuda.Event()
-                with torch.cuda.stream(p["st"]):   # exactly offs[F] rows, never the full capacity
-                    if total:
-                        for k, _ in self._COLS:
-                            p["cols"][k].copy_(self._out[k][p["b"], :total], non_blocking=True)
-                    ev.record(p["st"])
-                p["data"] = ev
-        while self._pending and self._pending[0]["data"] is not None and len(self._pending) > 2 * keep:
-            p = self._pending.popleft()
-            p["data"].synchronize()
-            self._count(self._droplet_frames(p["meta"], p["nact"], p["ndrop"], p["flags"], p["offs"],
-                                             {k: v.numpy().copy() for k, v in p["cols"].items()}))
-
-    # ------------------------------------------------------------------ processing
-    def process_frames(self, frames, meta):
-        """Find the droplets of ``frames`` (tensors of n elements on this consumer's device, issued on the current
-        stream) that are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank, idx, gevt,
-        photon_energy)``.  GPU: returns the consumer stream the batch runs on."""
-        return super().process_frames(frames, [tuple(m) + (None,) * (4 - len(m)) for m in meta])
-
-    def _check_batch(self, n):
-        if n > self.batch:
-            raise ValueError(f"droplets: {n} frames in a batch of at most {self.batch}")
-
-    def _meta_of(self, recs):
-        # a slot header carries NaN for "no photon energy", a queue item None
-        return [(r.rank, r.idx, r.gevt, None if r.photon_energy != r.photon_energy else r.photon_energy)
-                for r in recs]
+        self.frames_overflowed += over
+        self.frames_stored += len(df) - over
+        self.droplets_stored += int(df.offs[-1])
 
     def _launch_slots(self, C, slots, b, k, st):
-        offs, nact, ndrop, flags = self._split(self._hdr[b], len(slots))
+        offs, nact, ndrop, flags = self._split(self._hdr[b], len(slots)).values()
         P, H, W = self.phw
         pp = self.params
         o = self._out
@@ -1858,7 +1726,7 @@ class DropletConsumer(_BatchConsumer):
                          int(self._scratch[k].data_ptr()), self._scratch[k].numel(), int(st.cuda_stream))
 
     def _launch_tensors(self, frames, b, k, st):
-        offs, nact, ndrop, flags = self._split(self._hdr[b], len(frames))
+        offs, nact, ndrop, flags = self._split(self._hdr[b], len(frames)).values()
         o = self._out
         kernels.droplets([t.reshape(-1) for t in frames], self.phw, self.params, self.pix_cap, self.cap, nact, ndrop, flags,
                          offs, o["label"][b], o["npix"][b], o["adu"][b], o["sy"][b], o["sx"][b], o["qmax"][b],
@@ -1869,49 +1737,37 @@ class DropletConsumer(_BatchConsumer):
 
         x = torch.stack([t.reshape(-1) for t in frames])
         r = reference.droplet_reference(x, self.phw, self.params, self._mask_np, self.pix_cap, self.cap)
-        self._count(self._droplet_frames(meta, r.nact.numpy(), r.ndrop.numpy(), r.flags.numpy(), r.offs.numpy(),
-                                         {k: getattr(r, k).numpy() for k, _ in self._COLS}))
-
-    def take_results(self) -> list:
-        """The finished batches collected so far (oldest first); they are removed from :attr:`results`."""
-        with self._lock:
-            out, self.results = self.results, []
-        return out
+        self._collect(self._frames_of(meta, {k: getattr(r, k).numpy() for k in ("offs", "nact", "ndrop", "flags")},
+                                      {k: getattr(r, k).numpy() for k, _ in self._COLS}))
 
     def metrics(self) -> dict:
         return {"frames_consumed": self.frames, "frames_stored": self.frames_stored,
                 "frames_overflowed": self.frames_overflowed, "droplets_stored": self.droplets_stored}
 
-    def synchronize(self):
-        """Wait for every batch and collect it.  Returns the list of finished batches not taken yet."""
-        if self.gpu:
-            self._advance(keep=0)
-            self._advance(keep=0)   # first pass issues the last data copies, second collects them
-            self.sync_streams()
-        return self.results
 
-
-class CubeConsumer(_BatchConsumer):
+class CubeConsumer(_RunAccumulator):
     """Consumer engine: batches of leased slots -> K-15 cube (csrc/cube.hip) -> stream-ordered release.
 
     Per run and BIN of a per-event scalar (``binning``: :class:`psana_ray_amd.cube.CubeBinning`, from the
     photon energy or from the global event number): per-pixel count / sum / sum of squares of the quantised
     calibrated value inside ``[vmin, vmax]`` -- integers, so the result is exact in any frame order.  A
     frame's bin is computed on the HOST from its slot header before the launch; a frame without a bin is
-    dropped (not read).  The kernel owns a pixel per launch and uses no atomics, so every consumer stream
-    has its OWN accumulator set; :meth:`synchronize` adds the sets on the device and copies one result to
-    the host.  When the sets of all streams do not fit ``acc_budget`` bytes (default: half of the free HBM)
-    the consumer runs on one stream."""
+    dropped (not read).  One accumulator set per consumer stream (:class:`_RunAccumulator`):
+    :meth:`synchronize` returns the dict of ``frames`` int64 [B], ``cnt`` int32 / ``sum`` int64 / ``sq``
+    int64 [B, n].  When the sets of all streams do not fit ``acc_budget`` bytes (default: half of the free
+    HBM) the consumer runs on one stream."""
 
     name = "cube"
     wants_meta = True
+    meta_fields = 4
+    bound_text = "max_frames = {} (the int32 count and the int64 sum of squares)"
 
     def __init__(self, endpoint: QueueEndpoint, frame_shape, binning, vmin: Optional[float] = None,
                  vmax: Optional[float] = None, frac_bits: Optional[int] = None, detector: str = "",
                  layout: str = "calib", batch: Optional[int] = None, stream_kind: str = CONSUMER_STREAM_KIND,
                  streams: int = CONSUMER_STREAMS, ranks_per_gpu: Optional[int] = None, check_ring: bool = True,
                  acc_budget: Optional[int] = None):
-        """frame_shape: the shape of a (calibrated) frame.  check_ring=False: the queue carries RAW
+        """frame_shape: the shape of a (calibrated) frame.  check_ring=False: the ring holds RAW
         frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
         from . import cube as _cube
         from .ops import reference as _ref
@@ -1929,11 +1785,7 @@ class CubeConsumer(_BatchConsumer):
         self.nbins = binning.nbins
         self.detector, self.layout = str(detector), str(layout)
         if check_ring:
-            if endpoint.ring.dtype != torch.float32:
-                raise ValueError(f"cube: the queue carries {endpoint.ring.dtype} frames, the cube needs calibrated "
-                                 "float32 ones")
-            if int(np.prod(endpoint.ring.frame_shape)) != self.n:
-                raise ValueError(f"cube: frames of {self.shape} for queue frames {tuple(endpoint.ring.frame_shape)}")
+            self._check_ring(endpoint, "the cube needs calibrated float32 ones")
         self.set_bytes = _cube.accumulator_set_bytes(self.nbins, self.n)
         dev = endpoint.ring.device
         if dev.type == "cuda":
@@ -1951,45 +1803,15 @@ class CubeConsumer(_BatchConsumer):
         self.rows = []            # per batch: ([(rank, idx, gevt, photon_energy), ...], bins int32 [n])
         self._bins = None         # the bins of the batch being launched
         self._pending = None      # the meta of the batch process_frames hands to _launch_tensors
-        self._host = self._new_host()
-        if self.gpu:
-            B, n = self.nbins, self.n
-            # one accumulator set per stream; set k is only ever touched by launches on stream k
-            self._acc = [(torch.zeros(B, dtype=torch.int64, device=dev),
-                          torch.zeros((B, n), dtype=torch.int32, device=dev),
-                          torch.zeros((B, n), dtype=torch.int64, device=dev),
-                          torch.zeros((B, n), dtype=torch.int64, device=dev)) for _ in self.streams]
 
-    def _new_host(self) -> dict:
-        B, n = self.nbins, self.n
-        return {"frames": np.zeros(B, np.int64), "cnt": np.zeros((B, n), np.int32),
-                "sum": np.zeros((B, n), np.int64), "sq": np.zeros((B, n), np.int64)}
-
-    def _check_bound(self, n: int):
-        if self.frames + n > self.max_frames:
-            raise ValueError(f"cube: {self.frames} + {n} frames would take the run past max_frames = "
-                             f"{self.max_frames} (the int32 count and the int64 sum of squares)")
-
-    def _check_batch(self, n):
-        if n > self.batch:
-            raise ValueError(f"cube: {n} frames in a batch of at most {self.batch}")
-        self._check_bound(n)
-
-    def _limit(self, n_max):
-        self._check_bound(1)   # before any lease
-        return max(1, min(n_max, self.max_frames - self.frames))
+    def _fields(self):
+        b, s = (self.nbins,), (self.nbins, self.n)
+        return (_Field("frames", b, torch.int64, np.int64), _Field("cnt", s, torch.int32, np.int32),
+                _Field("sum", s, torch.int64, np.int64), _Field("sq", s, torch.int64, np.int64))
 
     def process_frames(self, frames, meta):
-        """Accumulate ``frames`` (tensors of n elements on this consumer's device, issued on the current
-        stream) that are not queue items -- e.g. frames calibrated on read.  ``meta``: their ``(rank, idx,
-        gevt, photon_energy)``.  GPU: returns the consumer stream the batch runs on."""
-        self._pending = [tuple(m) + (None,) * (4 - len(m)) for m in meta]
+        self._pending = self._pad_meta(meta)   # _launch_tensors bins the batch from it
         return super().process_frames(frames, self._pending)
-
-    def _meta_of(self, recs):
-        # a slot header carries NaN for "no photon energy", a queue item None
-        return [(r.rank, r.idx, r.gevt, None if r.photon_energy != r.photon_energy else r.photon_energy)
-                for r in recs]
 
     def _launch_slots(self, C, slots, b, k, st):
         # the bins come from the slot headers (a host read), before the native call
@@ -2017,45 +1839,17 @@ class CubeConsumer(_BatchConsumer):
 
         bins = self.binning.bin_of_meta(meta)
         x = torch.stack([t.reshape(-1) for t in frames])
-        nfr, cnt, s, sq = reference.cube_accumulate_reference(x, bins, self.nbins, self.vmin, self.vmax,
-                                                              self.frac_bits)
-        h = self._host
-        h["frames"] += nfr.numpy()
-        h["cnt"] += cnt.numpy()
-        h["sum"] += s.numpy()
-        h["sq"] += sq.numpy()
+        self._add(reference.cube_accumulate_reference(x, bins, self.nbins, self.vmin, self.vmax, self.frac_bits))
         self._keep_rows(meta, bins)
-
-    def synchronize(self) -> dict:
-        """Wait for every batch, add the per-stream accumulator sets ON THE DEVICE (exact: a count of the run
-        is at most its frames, which the bound keeps inside an int32) and copy the one result to the host.
-        Returns the dict of ``frames`` int64 [B], ``cnt`` int32 / ``sum`` int64 / ``sq`` int64 [B, n]."""
-        if self.gpu:
-            self.sync_streams()
-            with torch.cuda.device(self.device):
-                host = {}
-                for i, name in enumerate(("frames", "cnt", "sum", "sq")):
-                    total = self._acc[0][i]
-                    if len(self._acc) > 1:
-                        total = total.clone()
-                        for acc in self._acc[1:]:
-                            total += acc[i]
-                    host[name] = total.cpu().numpy()
-                    del total
-                self._host = host
-        return self._host
 
     def stats(self):
         """The (synchronised) run as a :class:`psana_ray_amd.cube.CubeStats`."""
         from .cube import CubeStats
 
         h = self.synchronize()
-        meta = [m for ms, _ in self.rows for m in ms]
-        bins = np.concatenate([b for _, b in self.rows]) if self.rows else np.zeros(0, np.int32)
+        bins = self._cat([b for _, b in self.rows], np.zeros(0, np.int32))
         bg = self.binning
         return CubeStats(self.detector, self.layout, self.shape, self.vmin, self.vmax, self.frac_bits, bg.by,
                          self.nbins, bg.edges, bg.table_sha256, h["frames"].copy(), self.dropped, h["cnt"].copy(),
-                         h["sum"].copy(), h["sq"].copy(), rank=[m[0] for m in meta], idx=[m[1] for m in meta],
-                         gevt=[m[2] for m in meta],
-                         photon_energy=[float("nan") if m[3] is None else float(m[3]) for m in meta],
+                         h["sum"].copy(), h["sq"].copy(), **self._meta_columns([m for ms, _ in self.rows for m in ms]),
                          bin=bins.astype(np.int16))

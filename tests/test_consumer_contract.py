@@ -1,6 +1,7 @@
-"""The surface the four consumer engines of psana_ray_amd.pipeline share (poll / process_frames /
-metrics / synchronize over pipeline._BatchConsumer), each against its golden model in ops.reference:
-on a CPU endpoint anywhere, and on the GPU through the ring-slot path and the tensor path in one run."""
+"""The surface the consumer engines of psana_ray_amd.pipeline share (poll / process_frames / metrics /
+synchronize over pipeline._BatchConsumer and its two bases, _RunAccumulator and _PackedRows); the first
+four (KINDS) each against its golden model in ops.reference: on a CPU endpoint anywhere, and on the GPU
+through the ring-slot path and the tensor path in one run."""
 import functools
 
 import numpy as np
@@ -25,8 +26,11 @@ PARAMS = PeakFinderParams(thr_peak=HIT_THR_PEAK, son_min=HIT_SON)
 NBINS, ADU = 32, (3, 16000)
 CAP = 450                        # some of the frames keep more pixels than this: they overflow
 KINDS = ["peak", "radial", "dark", "sparse", "sparse_hits"]
-CLASSES = [pipeline.PeakFinderConsumer, pipeline.RadialProfileConsumer, pipeline.DarkStatsConsumer,
-           pipeline.SparseFrameConsumer]
+RUN_ACCUMULATORS = [pipeline.DarkStatsConsumer, pipeline.PowderConsumer, pipeline.PixelHistConsumer,
+                    pipeline.PhotonConsumer, pipeline.CubeConsumer]
+PACKED_ROWS = [pipeline.SparseFrameConsumer, pipeline.DropletConsumer]
+CLASSES = [pipeline.PeakFinderConsumer, pipeline.RadialProfileConsumer, pipeline.RoiConsumer,
+           *RUN_ACCUMULATORS, *PACKED_ROWS]
 
 
 @functools.lru_cache(maxsize=None)
@@ -170,13 +174,28 @@ def test_peak_counts_have_margin():
 
 
 def test_one_loop_for_every_consumer():
-    """poll / process / sync_streams / _next exist once, in the base; only the dark consumer limits a poll."""
-    base = pipeline._BatchConsumer
+    """poll / process / sync_streams / _next exist once, in the base, and no engine has a _meta_of of its own;
+    the run bound and the combine of the per-stream sets exist once, in _RunAccumulator; the two-step drain
+    exists once, in _PackedRows; no other engine limits a poll."""
+    base, acc, rows = pipeline._BatchConsumer, pipeline._RunAccumulator, pipeline._PackedRows
+    assert len(CLASSES) == len(set(CLASSES)) == 10
     for cls in CLASSES:
         assert issubclass(cls, base)
-        for name in ("poll", "process", "sync_streams", "_next"):
+        for name in ("poll", "process", "sync_streams", "_next", "_meta_of"):
             assert getattr(cls, name) is getattr(base, name), (cls, name)
-        assert ("_limit" in vars(cls)) == (cls is pipeline.DarkStatsConsumer)
+        assert "_meta_of" not in vars(cls)
+        assert issubclass(cls, acc) == (cls in RUN_ACCUMULATORS) and issubclass(cls, rows) == (cls in PACKED_ROWS)
+    for name in ("_limit", "_check_bound", "synchronize"):
+        assert name in vars(acc), name
+        for cls in RUN_ACCUMULATORS:
+            assert name not in vars(cls) and getattr(cls, name) is getattr(acc, name), (cls, name)
+    for name in ("_launched", "_advance", "take_results", "synchronize"):
+        assert name in vars(rows), name
+        for cls in PACKED_ROWS:
+            assert name not in vars(cls) and getattr(cls, name) is getattr(rows, name), (cls, name)
+    for cls in CLASSES:
+        if cls not in RUN_ACCUMULATORS:
+            assert cls._limit is base._limit, cls
 
 
 @pytest.mark.parametrize("kind", KINDS)
