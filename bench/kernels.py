@@ -717,6 +717,84 @@ def main(argv=None):
                         "rounds_us_per_batch": [round(t[0] * 1e6, 2) for t in t_roi[k, sp]],
                         "vs_read_floor": round(mc[0] / mr[0], 3), "vs_powder": round(mc[0] / mp[0], 3),
                         "vs_empty_launch": round(mc[0] / me[0], 3)}, frames=FR)
+    if want("roibin"):
+        # K-17 roibin: 64 SEPARATELY allocated calib frames, alternating in the same process with the read floor and
+        # powder(NC=1) on the SAME frames -- the median round of each.  The binning kernel (headers + codes, phase 1)
+        # at B = 1, 2, 4 with about 100 hand-made records per frame; the box kernel (phase 2) at about 100 and at 2048
+        # records per frame, R = 4; the whole call at B = 2.  Bytes: the frame plus 2 B per code (binning); per box
+        # the record read twice, 36 B of ctr + rec and (2R+1)^2 words read and written (boxes).
+        from psana_ray_amd.ops.reference import (POWDER_FRAC_BITS, POWDER_QMAX_NONE, POWDER_THR_ABOVE, POWDER_VMAX,
+                                                 POWDER_VMIN, validate_roibin_params)
+
+        FR, rounds, MP, R = 64, 5, 2048, 4
+        C = _ext.load()
+        P, H, W = spec.frame_shape
+        rraw = [pool[i % pool.shape[0]].to(dev).clone() for i in range(FR)]
+        rfl = [torch.empty(spec.frame_shape, dtype=torch.float32, device=dev) for _ in range(FR)]
+        cal.run(rraw, rfl)
+        torch.cuda.synchronize()
+        del rraw
+        rflat = [t.reshape(-1) for t in rfl]
+        fp64 = [int(t.data_ptr()) for t in rfl]
+        sums = torch.zeros(FR, dtype=torch.float32, device=dev)
+        pacc = (torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros((1, npix), dtype=torch.int32, device=dev),
+                torch.zeros((1, npix), dtype=torch.int64, device=dev), torch.zeros((1, npix), dtype=torch.int64, device=dev),
+                torch.full((1, npix), POWDER_QMAX_NONE, dtype=torch.int32, device=dev),
+                torch.zeros((1, npix), dtype=torch.int32, device=dev))
+        rng = np.random.default_rng(0)
+        rec = rng.random((FR, MP, 8)).astype(np.float32)
+        rec[:, :, 0] = rng.integers(0, P, (FR, MP))
+        rec[:, :, 1] = rng.integers(0, H, (FR, MP))
+        rec[:, :, 2] = rng.integers(0, W, (FR, MP))
+        peaks = torch.from_numpy(rec).to(dev)
+        cnt = {"100": torch.from_numpy(rng.integers(80, 121, FR).astype(np.int32)).to(dev),
+               "2048": torch.full((FR,), MP, dtype=torch.int32, device=dev)}
+        Wn = 2 * R + 1
+        hd = {k: torch.zeros(FR, dtype=torch.int32, device=dev) for k in ("npk", "nbox", "nbad", "nsat")}
+        hd["flags"] = torch.zeros(FR, dtype=torch.uint8, device=dev)
+        hd["offs"] = torch.zeros(FR + 1, dtype=torch.int64, device=dev)
+        cols = {"ctr": torch.zeros(FR * MP, dtype=torch.int32, device=dev),
+                "rec": torch.zeros((FR * MP, 8), dtype=torch.float32, device=dev),
+                "box": torch.zeros((FR * MP, Wn, Wn), dtype=torch.float32, device=dev)}
+        pr = {B: validate_roibin_params(bin=B, radius=R, max_peaks=MP) for B in (1, 2, 4)}
+        codes = {B: torch.zeros((FR, P, -(-H // B), -(-W // B)), dtype=torch.int16, device=dev) for B in (1, 2, 4)}
+
+        def rb(B, which, phases):
+            def fn():
+                kernels.roibin(rflat, spec.frame_shape, pr[B], peaks, cnt[which], codes[B], **hd, **cols, _phases=phases)
+            return fn
+
+        cases = [(f"roibin bin(B={B})", B, "100", 1) for B in (1, 2, 4)] + \
+                [(f"roibin boxes(~{w} peaks, R={R})", 2, w, 2) for w in ("100", "2048")] + \
+                [("roibin(B=2, ~100 peaks)", 2, "100", 3)]
+        t_read, t_pow, t_rb = [], [], [[] for _ in cases]
+        for _ in range(rounds):
+            t_read.append(timeit(lambda: C.read_f32(fp64, npix, 16, False, int(sums.data_ptr()), _ext.stream_handle()),
+                                 a.iters))
+            for t, v in zip(pacc, (0, 0, 0, 0, POWDER_QMAX_NONE, 0)):
+                t.fill_(v)
+            t_pow.append(timeit(lambda: kernels.powder_accumulate(rflat, POWDER_VMIN, POWDER_VMAX, POWDER_FRAC_BITS,
+                                                                  POWDER_THR_ABOVE, *pacc), a.iters))
+            for k, (_name, B, which, phases) in enumerate(cases):
+                if phases == 2:
+                    rb(B, which, 1)()   # the headers of this record set
+                t_rb[k].append(timeit(rb(B, which, phases), a.iters))
+        med = lambda ts: sorted(ts)[rounds // 2]   # noqa: E731
+        us = lambda ts: [round(t[0] * 1e6 / FR, 3) for t in ts]   # noqa: E731
+        mr, mp = med(t_read), med(t_pow)
+        fbytes = FR * npix * 4
+        report("read_f32 reference (K=16)", mr, fbytes, {"rounds_us_per_frame": us(t_read)}, frames=FR)
+        report("powder(NC=1)", mp, fbytes + npix * 56,
+               {"rounds_us_per_frame": us(t_pow), "vs_read_floor": round(mp[0] / mr[0], 3)}, frames=FR)
+        for k, (name, B, which, phases) in enumerate(cases):
+            mc = med(t_rb[k])
+            nb = int(cnt[which].sum())
+            nbytes = (fbytes + codes[B].numel() * 2 if phases & 1 else 0) + \
+                     (nb * (32 + 36 + 8 * Wn * Wn) if phases & 2 else 0)
+            report(name, mc, nbytes,
+                   {"bin": B, "boxes": nb, "rounds_us_per_frame": us(t_rb[k]), "us_per_batch": round(mc[0] * 1e6, 2),
+                    "bytes_vs_read_floor": round(nbytes / fbytes, 3), "vs_read_floor": round(mc[0] / mr[0], 3),
+                    "vs_powder": round(mc[0] / mp[0], 3)}, frames=FR)
     if want("h2d"):
         C = _ext.load()
         hp = src.pool

@@ -99,7 +99,7 @@ static FramePtrs make_ptrs(const std::vector<uint64_t>& in, const std::vector<ui
 }
 
 // The consumers' ring-slot bindings (peakfind_slots, radial_slots, dark_slots, sparsify_slots,
-// powder_slots, pixel_hist_slots, photons_slots, droplets_slots, cube_slots, roi_slots): the two
+// powder_slots, pixel_hist_slots, photons_slots, droplets_slots, cube_slots, roi_slots, roibin_slots): the two
 // checks they share, then fn(index of the chunk's first slot, its slot pointers) for every chunk of at
 // most kMaxFrames slots.
 template <class Fn>
@@ -599,6 +599,43 @@ PYBIND11_MODULE(_C, m) {
   m.def("roi_plan_strips", &pr::roi_plan_strips, py::arg("rects"), py::arg("P"), py::arg("H"), py::arg("W"),
         "the strips of a K-16 plan, 8 int32 words each: r, p * H + y, rows, x0, x1, y, offx, offy + dy");
   m.attr("ROI_MAX_RECTS") = pr::kRoiMaxRects;
+
+  m.def("roibin",
+        [](const std::vector<uint64_t>& in, int P, int H, int W, int B, float inv, float vmin, float vmax, int R,
+           int min_peaks, int max_peaks, uint64_t mask, uint64_t peaks, uint64_t counts, uint64_t codes, uint64_t npk,
+           uint64_t nbox, uint64_t nbad, uint64_t nsat, uint64_t flags, uint64_t offs, uint64_t ctr, uint64_t rec,
+           uint64_t box, uint64_t stream, int phases) {
+          pr::launch_roibin(make_ptrs(in, in), (int)in.size(), P, H, W, B, inv, vmin, vmax, R, min_peaks, max_peaks, mask,
+                            peaks, counts, codes, npk, nbox, nbad, nsat, flags, offs, ctr, rec, box, stream, phases);
+        },
+        py::arg("in_ptrs"), py::arg("P"), py::arg("H"), py::arg("W"), py::arg("bin"), py::arg("inv"), py::arg("vmin"),
+        py::arg("vmax"), py::arg("radius"), py::arg("min_peaks"), py::arg("max_peaks"), py::arg("mask"), py::arg("peaks"),
+        py::arg("counts"), py::arg("codes"), py::arg("npk"), py::arg("nbox"), py::arg("nbad"), py::arg("nsat"),
+        py::arg("flags"), py::arg("offs"), py::arg("ctr"), py::arg("rec"), py::arg("box"), py::arg("stream"),
+        py::arg("phases") = 3,
+        "K-17 roibin of up to 64 frames: header words, the int16 codes of kept frames and the peak boxes");
+  // consumer hot path: ring slots -> roibin batch (headers + codes, boxes), one native call
+  m.def("roibin_slots",
+        [](const pr::SlotPool& pool, int64_t slot_bytes, const std::vector<int>& slots, int P, int H, int W, int B,
+           float inv, float vmin, float vmax, int R, int min_peaks, int max_peaks, uint64_t mask, uint64_t peaks,
+           uint64_t counts, uint64_t codes, uint64_t npk, uint64_t nbox, uint64_t nbad, uint64_t nsat, uint64_t flags,
+           uint64_t offs, uint64_t ctr, uint64_t rec, uint64_t box, uint64_t stream) {
+          const int ns = (int)slots.size();   // one launch: the batch's offs and boxes are packed together
+          pr::check(ns >= 1 && ns <= pr::kMaxFrames, "roibin_slots: 1..64 slots per batch");
+          for_slot_chunks(pool, slot_bytes, slots, (int64_t)P * H * W * 4, "roibin_slots",
+                          [&](int, const std::vector<uint64_t>& in) {
+                            pr::launch_roibin(make_ptrs(in, in), (int)in.size(), P, H, W, B, inv, vmin, vmax, R, min_peaks,
+                                              max_peaks, mask, peaks, counts, codes, npk, nbox, nbad, nsat, flags, offs,
+                                              ctr, rec, box, stream);
+                          });
+        },
+        py::arg("pool"), py::arg("slot_bytes"), py::arg("slots"), py::arg("P"), py::arg("H"), py::arg("W"),
+        py::arg("bin"), py::arg("inv"), py::arg("vmin"), py::arg("vmax"), py::arg("radius"), py::arg("min_peaks"),
+        py::arg("max_peaks"), py::arg("mask"), py::arg("peaks"), py::arg("counts"), py::arg("codes"), py::arg("npk"),
+        py::arg("nbox"), py::arg("nbad"), py::arg("nsat"), py::arg("flags"), py::arg("offs"), py::arg("ctr"),
+        py::arg("rec"), py::arg("box"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.attr("ROIBIN_MAX_PEAKS") = pr::kRoibinMaxPeaks;
+  m.attr("ROIBIN_MAX_RADIUS") = pr::kRoibinMaxRadius;
 
   m.def("copy_h2d_kernel",
         [](uint64_t dst, uint64_t src, int64_t bytes, int workgroups, uint64_t stream) {

@@ -175,4 +175,19 @@ struct RoiPlan {
 };
 void launch_roi(const FramePtrs& fp, int nframes, const RoiPlan& plan, float vmin, float vmax, int frac_bits,
                 uint64_t mask, uint64_t rows, uint64_t projx, uint64_t projy, uint64_t stream);
+// K-17 roibin (csrc/roibin.hip): of up to kMaxFrames float32 frames of shape [P, H, W], given the peak finder's
+// peaks float32 [F, max_peaks, 8] and counts int32 [F] on the device, every frame with counts[f] >= min_peaks
+// as codes int16 [F, P, Hb, Wb] (the B x B block means of q = rintf(v * inv) over the pixels with vmin <= v <=
+// vmax that the mask keeps, rounded half up, clamped to +-32767, -32768 = no pixel) and one box per valid
+// record, ordered by centre: ctr int32, rec uint32 [.., 8], box uint32 [.., 2R+1, 2R+1] of F * max_peaks rows,
+// frame f's at offs[f] .. offs[f + 1] (offs int64 [F + 1]).  npk / nbox / nbad / nsat int32 [F], flags uint8 [F]
+// (bit 0 = more peaks than max_peaks: no boxes, bit 1 = skipped, bit 2 = an invalid record).  A skipped frame is
+// not read and its code rows are not written.  One call is complete in itself: nothing needs clearing.
+constexpr int kRoibinMaxPeaks = 4096;   // the sort keys of a frame fit LDS
+constexpr int kRoibinMaxRadius = 7;
+void launch_roibin(const FramePtrs& fp, int nframes, int P, int H, int W, int B, float inv, float vmin, float vmax,
+                   int R, int min_peaks, int max_peaks, uint64_t mask, uint64_t peaks, uint64_t counts, uint64_t codes,
+                   uint64_t npk, uint64_t nbox, uint64_t nbad, uint64_t nsat, uint64_t flags, uint64_t offs,
+                   uint64_t ctr, uint64_t rec, uint64_t box, uint64_t stream,
+                   int phases = 3);   // measurements only: 1 = headers + codes, 2 = boxes of a batch just binned
 }  // namespace pr

@@ -50,7 +50,7 @@ def build_parser():
     ap.add_argument("--ray_namespace", type=str, default=DEFAULT_RAY_NAMESPACE)
     ap.add_argument("--queue_name", type=str, default=DEFAULT_QUEUE_NAME)
     ap.add_argument("--device", type=str, default=None)
-    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets", "cube", "roi", "train", "none"],
+    ap.add_argument("--task", type=str, default="print", choices=["print", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets", "cube", "roi", "roibin", "train", "none"],
                     help="train: online PeakNetLite training from peak-finder labels (trainer.py); radial: radial "
                          "profile I(r) / I(q) of every frame + run accumulator (--nbins ... --radial_mask); dark: "
                          "per-pixel dark-run statistics of a RAW queue (--adu_min / --adu_max); sparse: zero-suppressed "
@@ -60,7 +60,9 @@ def build_parser():
                          "of the calibrated frames (--adu_per_photon ... --photon_roi); droplets: connected clusters of "
                          "pixels above a threshold per frame (--drop_thr_low ... --drop_mask); cube: per-pixel run sums "
                          "per bin of the photon energy or of a per-event table (--cube_by ... --cube_frac_bits); roi: per frame "
-                         "the sum, centre of mass, maximum and projections of up to 16 rectangles (--roi ... --roi_mask)")
+                         "the sum, centre of mass, maximum and projections of up to 16 rectangles (--roi ... --roi_mask); roibin: per "
+                         "hit a lossless box around every peak plus the frame binned to int16 codes (--rb_bin ... --rb_mask, "
+                         "--min_peaks)")
     ap.add_argument("--lr", type=float, default=1e-3, help="--task train: AdamW learning rate")
     ap.add_argument("--save", type=str, default=None, help="--task train: write the model state_dict here")
     ap.add_argument("--ddp", action="store_true",
@@ -84,7 +86,8 @@ def build_parser():
                          "(psana_ray_amd.photons.PhotonStats npz) when --task photons; the droplet lists "
                          "(psana_ray_amd.droplets.DropletFrames npz) when --task droplets; the cube "
                          "(psana_ray_amd.cube.CubeStats npz) when --task cube; the per-frame ROI records "
-                         "(psana_ray_amd.roi.RoiFrames npz) when --task roi")
+                         "(psana_ray_amd.roi.RoiFrames npz) when --task roi; the peak boxes and binned codes "
+                         "(psana_ray_amd.roibin.RoibinFrames npz) when --task roibin")
     g = ap.add_argument_group("--task radial")
     g.add_argument("--nbins", type=int, default=512, help="radial bins (1 .. 4096)")
     g.add_argument("--center", type=str, default=None, help="beam centre Y,X in image pixels (default: image centre)")
@@ -109,6 +112,7 @@ def build_parser():
     add_droplet_arguments(ap)
     add_cube_arguments(ap)
     add_roi_arguments(ap)
+    add_roibin_arguments(ap)
     ap.add_argument("--timeout", type=float, default=300.0)
     ap.add_argument("--metrics_interval", type=float, default=10.0, help="seconds between rate lines; 0 disables")
     ap.add_argument("--metrics_json", type=str, default=None, help="append per-interval metrics as JSON lines")
@@ -132,6 +136,66 @@ def add_sparse_arguments(ap):
     g.add_argument("--part_frames", type=int, default=0,
                    help="K > 0: write parts STEM.00000.npz, ... of at most K frames while running, instead of one "
                         "file at the end")
+
+
+def add_roibin_arguments(ap):
+    """The flags of ``--task roibin`` (the producer CLI's ``--consumer_task roibin`` takes the same); the hit filter
+    is --min_peaks / --thr_peak / --son_min and the parts are --part_frames, as for ``--task sparse``."""
+    g = ap.add_argument_group("--task roibin")
+    g.add_argument("--rb_bin", type=int, default=2, choices=[1, 2, 4],
+                   help="the frame is binned B x B outside the peak boxes (default 2)")
+    g.add_argument("--rb_step", type=float, default=1.0,
+                   help="a code is the block mean in units of step, to within step / 2 (default 1.0); "
+                        "max(|vmin|, |vmax|) / step must stay below 2^25")
+    g.add_argument("--rb_box", type=int, default=4,
+                   help="R in 0 .. 7: the lossless box around a peak is (2R+1) x (2R+1) pixels (default 4)")
+    g.add_argument("--rb_vmin", type=float, default=-float(2 ** 20),
+                   help="value window: pixels below do not count in a block (default -2^20)")
+    g.add_argument("--rb_vmax", type=float, default=float(2 ** 20),
+                   help="value window: pixels above do not count in a block (default 2^20)")
+    g.add_argument("--rb_mask", type=str, default=None,
+                   help=".npy keep-mask of the frames' shape: non-zero = keep (default: every pixel)")
+
+
+def load_keep_mask(flag, path, shape):
+    """``flag`` (``--rb_mask``): a uint8 keep-mask [n] of the frames' shape (an image may come without its leading
+    axis of 1), or None; ValueError for another shape."""
+    import numpy as np
+
+    if not path:
+        return None
+    mask = np.load(path)   # allow_pickle stays False
+    shape = tuple(shape)
+    if tuple(mask.shape) != shape and not (shape[0] == 1 and tuple(mask.shape) == shape[1:]):
+        raise ValueError(f"{flag} is {tuple(mask.shape)}, the frames are {shape}")
+    return (mask != 0).astype(np.uint8).reshape(-1)
+
+
+def roibin_consumer(args, endpoint, shape, name, layout, check_ring=True):
+    """The RoibinConsumer of ``--task roibin`` / ``--consumer_task roibin`` from the ``--rb_*`` flags."""
+    from .config import PeakFinderParams
+    from .pipeline import RoibinConsumer
+
+    return RoibinConsumer(endpoint, shape, bin=args.rb_bin, step=args.rb_step, vmin=args.rb_vmin, vmax=args.rb_vmax,
+                          radius=args.rb_box, mask=load_keep_mask("--rb_mask", args.rb_mask, shape),
+                          min_peaks=args.min_peaks,
+                          peak_params=PeakFinderParams(thr_peak=getattr(args, "thr_peak", 20.0),
+                                                       son_min=getattr(args, "son_min", 5.0)),
+                          detector=name, layout=layout, batch=args.batch, check_ring=check_ring)
+
+
+def roibin_start_line(cid, cons) -> str:
+    p = cons.params
+    _P, Hb, Wb = cons.code_shape
+    return (f"Consumer {cid} roibin: bin={p.bin} step={p.step:g} window=[{p.vmin:g},{p.vmax:g}] box={2 * p.radius + 1}x"
+            f"{2 * p.radius + 1} max_peaks={p.max_peaks} min_peaks={p.min_peaks} codes={Hb}x{Wb} "
+            f"frame_bytes={cons.frame_bytes} batch={cons.batch}")
+
+
+def roibin_final_line(cid, cons) -> str:
+    m = cons.metrics()
+    return (f"Consumer {cid} roibin: frames={cons.frames} kept={m['frames_kept']} skipped={m['frames_skipped']} "
+            f"boxes={m['boxes']} overflowed={m['frames_overflowed']} saturated={m['saturated']}")
 
 
 def add_powder_arguments(ap):
@@ -582,15 +646,20 @@ def run_dark(args, reader, stop, progress) -> int:
 
 
 class SparseWriter:
-    """Where the finished batches of --task sparse go.  ``part_frames == 0``: everything is kept and
+    """Where the finished batches of --task sparse (and, with ``concat`` = roibin.concat, of --task roibin) go:
+    frame objects with ``__len__``, ``select`` and ``save`` that ``concat`` joins.  ``part_frames == 0``:
+    everything is kept and
     written to ``out`` by :meth:`close`.  ``part_frames = K > 0``: parts ``stem.00000.npz, ...`` of at
     most K frames, written by ONE background thread through a queue of depth 1 -- the run holds at
     most two parts in host memory (the one being filled and the one being written)."""
 
-    def __init__(self, out, part_frames: int = 0):
+    def __init__(self, out, part_frames: int = 0, concat=None):
         import queue
         import threading
 
+        if concat is None:
+            from .sparse import concat
+        self.concat = concat
         self.out = out
         self.part_frames = max(0, int(part_frames or 0))
         self.paths = []
@@ -607,15 +676,13 @@ class SparseWriter:
         return f"{stem}.{k:05d}.npz"
 
     def _work(self):
-        from . import sparse
-
         while True:
             job = self._q.get()
             if job is None:
                 return
             path, parts = job
             try:
-                sparse.concat(parts).save(path)
+                self.concat(parts).save(path)
             except Exception as e:  # noqa: BLE001 - reported by close()
                 self._error = e
 
@@ -626,7 +693,7 @@ class SparseWriter:
         self._q.put((path, parts))   # blocks while the previous part is still being written
 
     def add(self, batches):
-        """Finished batches (SparseFrames), oldest first."""
+        """Finished batches (frame objects), oldest first."""
         if not self.out:
             return
         for sf in batches:
@@ -644,10 +711,8 @@ class SparseWriter:
                     self._held, self._held_frames = [], 0
 
     def close(self, empty):
-        """Write what is left.  ``empty``: a SparseFrames of no frames with the run's parameters (a run
+        """Write what is left.  ``empty``: a frame object of no frames with the run's parameters (a run
         without frames still writes its file)."""
-        from . import sparse
-
         if not self.out:
             return
         if self.part_frames:
@@ -658,7 +723,7 @@ class SparseWriter:
             if self._error is not None:
                 raise self._error
         else:
-            sparse.concat(self._held or [empty]).save(self.out)
+            self.concat(self._held or [empty]).save(self.out)
             self.paths.append(self.out)
 
 
@@ -725,6 +790,39 @@ def run_sparse(args, reader, stop, progress) -> int:
     m = cons.metrics()
     print(f"Consumer {cid} sparse: frames={cons.frames} stored={m['frames_stored']} skipped={m['frames_skipped']} "
           f"overflowed={m['frames_overflowed']} pixels={m['pixels_stored']}", flush=True)
+    return rc
+
+
+def run_roibin(args, reader, stop, progress) -> int:
+    """--task roibin: peak boxes and binned codes until the end of the stream; ``progress["n"]`` counts frames."""
+    from . import roibin
+
+    cid = reader.consumer_id
+    if not _has_whole_frames(reader, "roibin", "peak boxes and binned frames"):
+        return 2
+    cal = reader.calibrator
+    try:
+        name, layout, shape = sparse_layout(reader, args, needs="roibin needs")
+    except ValueError as e:
+        log.error("--task roibin: %s", e)
+        return 2
+    if not name:
+        log.error("--task roibin: the session does not name its detector; pass --detector_name")
+        return 2
+    try:
+        cons = roibin_consumer(args, reader.endpoint, shape, name, layout, check_ring=cal is None)
+    except (ValueError, KeyError, OSError) as e:
+        log.error("--task roibin: %s", e)
+        return 2
+    print(roibin_start_line(cid, cons), flush=True)
+    writer = SparseWriter(args.out, args.part_frames, concat=roibin.concat)
+    rc = _drive(args, reader, stop, progress, cons,
+                raw_meta=None if cal is None else lambda it: (it.rank, it.idx, it.gevt, it.photon_energy),
+                each=lambda: writer.add(cons.take_results()))
+    cons.synchronize()
+    writer.add(cons.take_results())
+    writer.close(cons.empty())
+    print(roibin_final_line(cid, cons), flush=True)
     return rc
 
 
@@ -1005,7 +1103,7 @@ def main(argv=None) -> int:
         pf = None
         run_task = {"radial": run_radial, "dark": run_dark, "sparse": run_sparse, "powder": run_powder,
                     "hist": run_hist, "photons": run_photons, "droplets": run_droplets, "cube": run_cube,
-                    "roi": run_roi}.get(args.task)
+                    "roi": run_roi, "roibin": run_roibin}.get(args.task)
         if run_task is not None:   # the tasks that run a pipeline consumer to the end of the stream
             progress = {"n": 0}
             registry.register(args.task, lambda: {"frames_consumed": progress["n"]})

@@ -1,4 +1,4 @@
-"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-16).
+"""Validated torch-facing wrappers of the gfx950 HIP kernels (K-01..K-05, K-07..K-17).
 
 Every wrapper checks device / dtype / shape / contiguity / alignment on the host BEFORE the
 launch (a mis-shaped launch of a hand-written kernel can fault the GPU), splits batches into
@@ -768,6 +768,63 @@ def droplets(frames: Sequence[torch.Tensor], shape, params, cap_pix: int, cap: i
                0 if mask is None else _ptr(mask), _ptr(nact), _ptr(ndrop), _ptr(flags), _ptr(offs), _ptr(label),
                _ptr(npix), _ptr(adu), _ptr(sy), _ptr(sx), _ptr(qmax), _ptr(scratch),
                scratch.numel() * scratch.element_size(), s, int(_phases))
+
+
+def roibin(frames: Sequence[torch.Tensor], shape, params, peaks: torch.Tensor, counts: torch.Tensor,
+           codes: torch.Tensor, npk: torch.Tensor, nbox: torch.Tensor, nbad: torch.Tensor, nsat: torch.Tensor,
+           flags: torch.Tensor, offs: torch.Tensor, ctr: torch.Tensor, rec: torch.Tensor, box: torch.Tensor,
+           mask: Optional[torch.Tensor] = None, stream=None, _phases: int = 3):
+    """K-17 roibin (csrc/roibin.hip; contract: ops.reference.roibin_reference).
+    frames: F (1 .. 64) float32 tensors of ``shape`` = [P, H, W] (or [H, W]) on one GPU; ``params``: a
+    reference.RoibinParams; ``peaks`` float32 [F, max_peaks, 8] and ``counts`` int32 [F]: the peak finder's outputs
+    on the device.  Outputs (overwritten, no clearing needed): ``codes`` int16 [F, P, Hb, Wb] (the rows of frames
+    with counts[f] < min_peaks are NOT written), ``npk`` / ``nbox`` / ``nbad`` / ``nsat`` int32 [F], ``flags``
+    uint8 [F], ``offs`` int64 [F + 1], and the box columns ``ctr`` int32 [F * max_peaks], ``rec`` float32
+    [F * max_peaks, 8], ``box`` float32 [F * max_peaks, 2R+1, 2R+1] -- frame f's boxes at offs[f] .. offs[f + 1];
+    rows from offs[F] on are unspecified.  ``mask``: uint8 [n], non-zero = keep.  One call is complete in itself
+    and may run on any stream.  Everything is checked here, before any launch.  ``_phases`` (measurements): 1 =
+    headers and codes only, 2 = the boxes of a batch just binned."""
+    from .reference import RoibinParams, photon_shape, validate_roibin_params
+
+    what = "roibin"
+    if not isinstance(params, RoibinParams):
+        raise ValueError(f"{what}: params must be a RoibinParams (validate_roibin_params)")
+    d = params._asdict()
+    d.pop("inv")
+    rp = validate_roibin_params(what=what, **d)
+    P, H, W = photon_shape(shape, what)
+    n = P * H * W
+    B, R, MP = rp.bin, rp.radius, rp.max_peaks
+    Hb, Wb = -(-H // B), -(-W // B)
+    F = len(frames)
+    if not 1 <= F <= MAX_FRAMES:
+        raise ValueError(f"{what}: 1 .. {MAX_FRAMES} frames per launch, got {F}")
+    if _phases not in (1, 2, 3):
+        raise ValueError(f"{what}: _phases must be 1, 2 or 3")
+    if not isinstance(frames[0], torch.Tensor):
+        raise ValueError(f"{what}: frames must be tensors")
+    dev = frames[0].device
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: frames on {dev}, expected a GPU")
+    _check_frames(frames, torch.float32, n, dev, f"{what} in")
+    Wn = 2 * R + 1
+    for t, dt, shp, al, name in ((peaks, torch.float32, (F, MP, 8), 4, "peaks"), (counts, torch.int32, (F,), 4, "counts"),
+                                 (codes, torch.int16, (F, P, Hb, Wb), 8, "codes"), (npk, torch.int32, (F,), 4, "npk"),
+                                 (nbox, torch.int32, (F,), 4, "nbox"), (nbad, torch.int32, (F,), 4, "nbad"),
+                                 (nsat, torch.int32, (F,), 4, "nsat"), (flags, torch.uint8, (F,), 1, "flags"),
+                                 (offs, torch.int64, (F + 1,), 8, "offs"), (ctr, torch.int32, (F * MP,), 4, "ctr"),
+                                 (rec, torch.float32, (F * MP, 8), 4, "rec"),
+                                 (box, torch.float32, (F * MP, Wn, Wn), 4, "box")):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shp or t.dtype != dt or t.device != dev \
+                or not t.is_contiguous() or t.data_ptr() % al:
+            raise ValueError(f"{what}: {name} must be a contiguous, {al}-B aligned {dt} {list(shp)} tensor on {dev}")
+    pm = _photon_map(mask, n, dev, "mask", what)
+    C = _ext.load()
+    if C.ROIBIN_MAX_PEAKS < MP or C.ROIBIN_MAX_RADIUS < R:
+        raise RuntimeError(f"{what}: max_peaks / radius limits disagree with the extension")
+    C.roibin([_ptr(t) for t in frames], P, H, W, B, rp.inv, rp.vmin, rp.vmax, R, rp.min_peaks, MP, pm, _ptr(peaks),
+             _ptr(counts), _ptr(codes), _ptr(npk), _ptr(nbox), _ptr(nbad), _ptr(nsat), _ptr(flags), _ptr(offs),
+             _ptr(ctr), _ptr(rec), _ptr(box), _ext.stream_handle(stream), int(_phases))
 
 
 def mask_frames(frames: Sequence[torch.Tensor], zero: torch.Tensor, stream=None):

@@ -1116,3 +1116,223 @@ def roi_stats_reference(frames: torch.Tensor, shape, rects, vmin: float, vmax: f
             py.append(q.sum(dim=2))
     empty = torch.zeros((F, 0), dtype=torch.int64)
     return (torch.from_numpy(rows), torch.cat(px, dim=1) if px else empty, torch.cat(py, dim=1) if py else empty)
+
+
+# K-17 roibin: the contract's constants (docs/ARCHITECTURE.md, "Roibin: the contract")
+ROIBIN_BINS = (1, 2, 4)
+ROIBIN_BIN = 2
+ROIBIN_STEP = 1.0
+ROIBIN_RADIUS = 4
+ROIBIN_MAX_RADIUS = 7
+ROIBIN_MAX_PEAKS = 4096              # the sort keys of a frame fit LDS
+ROIBIN_MAX_FRAMES = 64
+ROIBIN_VMIN = POWDER_VMIN            # the K-08 window
+ROIBIN_VMAX = POWDER_VMAX
+ROIBIN_CODE_NONE = -32768            # the code of a block without a counting pixel
+ROIBIN_CODE_MAX = 32767              # codes are clamped to -32767 .. 32767
+ROIBIN_Q_BOUND = 2 ** 25             # max(|vmin|, |vmax|) * inv stays below it: 2 S + c fits an int32 at B = 4
+ROIBIN_FLAG_OVERFLOW = 1             # npk[f] > max_peaks: which records survived is arbitrary, so no boxes
+ROIBIN_FLAG_SKIPPED = 2              # counts[f] < min_peaks: the frame was neither read nor written
+ROIBIN_FLAG_BAD = 4                  # a record was not a pixel of the frame (counted in nbad)
+ROIBIN_NAN_BITS = 0x7FC00000         # a box cell outside the panel
+
+
+class RoibinParams(NamedTuple):
+    bin: int
+    step: float        # as float32
+    inv: float         # float32(1.0 / float64(step))
+    vmin: float
+    vmax: float
+    radius: int
+    max_peaks: int
+    min_peaks: int
+
+
+class RoibinBatch(NamedTuple):
+    npk: torch.Tensor      # int32 [F]
+    nbox: torch.Tensor     # int32 [F]
+    nbad: torch.Tensor     # int32 [F]
+    nsat: torch.Tensor     # int32 [F]
+    flags: torch.Tensor    # uint8 [F]
+    offs: torch.Tensor     # int64 [F + 1]
+    ctr: torch.Tensor      # int32 [K]
+    rec: torch.Tensor      # float32 [K, 8]
+    box: torch.Tensor      # float32 [K, 2R+1, 2R+1]
+    codes: torch.Tensor    # int16 [kept, P, Hb, Wb]: the kept frames only, in frame order
+
+
+def validate_roibin_params(bin=ROIBIN_BIN, step=ROIBIN_STEP, vmin=ROIBIN_VMIN, vmax=ROIBIN_VMAX, radius=ROIBIN_RADIUS,
+                           max_peaks=ROIBIN_MAX_PEAKS, min_peaks=0, what: str = "roibin") -> RoibinParams:
+    """The parameters as the values the kernel sees, with ``inv = float32(1.0 / float64(step))`` -- or ValueError.
+    Requires bin in {1, 2, 4}, a finite float32 step > 0 with a finite positive inv, a finite window vmin <= vmax
+    with ``max(|vmin|, |vmax|) * inv < 2^25`` (float32), radius in 0 .. 7, max_peaks in 1 .. 4096, min_peaks in
+    0 .. 2^31 - 1."""
+    if isinstance(bin, RoibinParams):
+        bin, step, _inv, vmin, vmax, radius, max_peaks, min_peaks = bin
+    try:
+        B, R = operator.index(bin), operator.index(radius)
+        mp, mn = operator.index(max_peaks), operator.index(min_peaks)
+    except TypeError:
+        raise ValueError(f"{what}: bin, radius, max_peaks and min_peaks must be integers") from None
+    if B not in ROIBIN_BINS:
+        raise ValueError(f"{what}: bin must be one of {ROIBIN_BINS}, got {B}")
+    if not 0 <= R <= ROIBIN_MAX_RADIUS:
+        raise ValueError(f"{what}: the box radius must be in 0 .. {ROIBIN_MAX_RADIUS}, got {R}")
+    if not 1 <= mp <= ROIBIN_MAX_PEAKS:
+        raise ValueError(f"{what}: max_peaks must be in 1 .. {ROIBIN_MAX_PEAKS}, got {mp}")
+    if not 0 <= mn < 2 ** 31:
+        raise ValueError(f"{what}: min_peaks must be in 0 .. 2^31 - 1, got {mn}")
+    try:
+        with np.errstate(over="ignore", under="ignore"):
+            st, lo, hi = float(np.float32(step)), float(np.float32(vmin)), float(np.float32(vmax))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: step, vmin and vmax must be numbers") from None
+    if not (np.isfinite(st) and st > 0.0):
+        raise ValueError(f"{what}: step must be finite and positive, got {step}")
+    with np.errstate(over="ignore", under="ignore", divide="ignore"):
+        inv = float(np.float32(1.0 / np.float64(st)))
+    if not (np.isfinite(inv) and inv > 0.0):
+        raise ValueError(f"{what}: the scale 1 / step = {inv} is not a finite positive float32")
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"{what}: the value window must be finite, got [{vmin}, {vmax}]")
+    if not lo <= hi:
+        raise ValueError(f"{what}: empty value window [{vmin}, {vmax}]")
+    with np.errstate(over="ignore"):
+        top = np.float32(max(abs(lo), abs(hi))) * np.float32(inv)
+    if not top < ROIBIN_Q_BOUND:
+        raise ValueError(f"{what}: max(|vmin|, |vmax|) / step = {float(top):g} must stay below 2^25 "
+                         "(the block sums are int32)")
+    return RoibinParams(B, st, inv, lo, hi, R, mp, mn)
+
+
+def roibin_code_shape(shape, bin, what: str = "roibin"):
+    """``(P, Hb, Wb)`` of the codes of frames of ``shape``: Hb = ceil(H / bin), Wb = ceil(W / bin)."""
+    P, H, W = photon_shape(shape, what)
+    B = int(bin)
+    return P, -(-H // B), -(-W // B)
+
+
+def roibin_frame_bytes(shape, params) -> int:
+    """Bytes of a kept frame's codes (what crosses to the host per kept frame, boxes aside)."""
+    P, Hb, Wb = roibin_code_shape(shape, params.bin)
+    return 2 * P * Hb * Wb
+
+
+def roibin_valid_records(rec: np.ndarray, shape) -> "tuple[np.ndarray, np.ndarray]":
+    """(valid bool [k], ctr int64 [k]) of float32 records [k, 8]: (p, y, x) finite, integral and inside the frame."""
+    P, H, W = shape
+    valid = np.ones(rec.shape[0], dtype=bool)
+    idx = []
+    with np.errstate(invalid="ignore"):
+        for col, dim in ((0, P), (1, H), (2, W)):
+            v = rec[:, col].astype(np.float64)
+            ok = np.isfinite(v) & (v >= 0) & (v < dim) & (np.floor(v) == v)
+            valid &= ok
+            idx.append(np.where(ok, v, 0).astype(np.int64))
+    ctr = (idx[0] * H + idx[1]) * W + idx[2]
+    return valid, np.where(valid, ctr, 0)
+
+
+def roibin_reference(frames: torch.Tensor, shape, peaks, counts, params=None, mask=None, **kw) -> RoibinBatch:
+    """K-17 golden: lossless peak boxes and binned codes.  ``frames``: [F, ...] float32 of ``shape`` = [P, H, W] (or
+    [H, W]), 1 <= F <= 64; ``peaks``: float32 [F, max_peaks, 8] and ``counts``: int32 [F], the peak finder's
+    outputs (or hand-made ones); ``params``: a RoibinParams, or the keywords of validate_roibin_params (max_peaks
+    must equal peaks.shape[1]); ``mask``: uint8 [n] or None, non-zero = keep.
+
+    Frame f is kept iff counts[f] >= min_peaks; a skipped frame has flags 2 and no codes.  Codes of a kept frame:
+    per B x B block (clipped to the panel) the sum S and the count c of q = int(round_half_even(v * inv)) over the
+    pixels the mask keeps with vmin <= v <= vmax (float32; NaN and +-inf never count); -32768 when c == 0, else
+    clamp(floor_div(2 S + c, 2 c), -32767, 32767), a clamped block adding 1 to nsat[f].  Boxes: npk = max(counts,
+    0); npk > max_peaks sets flag bit 0 and gives no boxes; otherwise the records whose (p, y, x) are finite,
+    integral and inside the frame (the others add 1 to nbad[f], flag bit 2), ordered by ctr = (p * H + y) * W + x
+    with ties by slot: ctr, a bit copy of the record, and the (2R+1)^2 window as bit copies, 0x7FC00000 outside
+    the panel.  offs = exclusive scan of nbox."""
+    what = "roibin"
+    if params is not None and (kw or not isinstance(params, RoibinParams)):
+        raise ValueError(f"{what}: give a RoibinParams or the keywords of validate_roibin_params, not both")
+    if params is not None:
+        kw = params._asdict()
+        kw.pop("inv")
+    rp = validate_roibin_params(what=what, **kw)
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.float32:
+        raise ValueError(f"{what}: frames must be a float32 tensor, got {getattr(frames, 'dtype', type(frames))}")
+    F = int(frames.shape[0]) if frames.dim() >= 1 else 0
+    if not 1 <= F <= ROIBIN_MAX_FRAMES:
+        raise ValueError(f"{what}: 1 .. {ROIBIN_MAX_FRAMES} frames per batch, got {F}")
+    P, H, W = photon_shape(shape, what)
+    n = P * H * W
+    x = frames.detach().cpu().reshape(F, -1)
+    if x.shape[1] != n:
+        raise ValueError(f"{what}: frames of {x.shape[1]} elements for the shape {(P, H, W)}")
+    x = x.reshape(F, P, H, W)
+    pk = peaks.detach().cpu() if isinstance(peaks, torch.Tensor) else torch.as_tensor(np.asarray(peaks))
+    ct = counts.detach().cpu() if isinstance(counts, torch.Tensor) else torch.as_tensor(np.asarray(counts))
+    if pk.dtype != torch.float32 or tuple(pk.shape) != (F, rp.max_peaks, 8):
+        raise ValueError(f"{what}: peaks must be float32 [{F}, {rp.max_peaks}, 8], got {pk.dtype} {list(pk.shape)}")
+    if ct.dtype != torch.int32 or tuple(ct.shape) != (F,):
+        raise ValueError(f"{what}: counts must be int32 [{F}], got {ct.dtype} {list(ct.shape)}")
+    mask, _roi, _R = validate_photon_maps((P, H, W), mask, None, None, what)
+    B, R = rp.bin, rp.radius
+    Hb, Wb = -(-H // B), -(-W // B)
+    cnt = ct.numpy().astype(np.int64)
+    kept = cnt >= rp.min_peaks
+    npk = np.maximum(cnt, 0)
+    over = kept & (npk > rp.max_peaks)
+
+    # codes of the kept frames
+    kf = np.nonzero(kept)[0]
+    xk = x[torch.from_numpy(kf)]
+    ok = (xk >= rp.vmin) & (xk <= rp.vmax)
+    if mask is not None:
+        ok &= torch.from_numpy(mask != 0).reshape(1, P, H, W)
+    q = torch.round(torch.where(ok, xk, torch.zeros_like(xk)) * rp.inv).to(torch.int32)   # one float32 multiply
+    qp = torch.zeros((len(kf), P, Hb * B, Wb * B), dtype=torch.int32)
+    cp = torch.zeros((len(kf), P, Hb * B, Wb * B), dtype=torch.int32)
+    qp[:, :, :H, :W] = q
+    cp[:, :, :H, :W] = ok.to(torch.int32)
+    S = qp.reshape(-1, P, Hb, B, Wb, B).sum(dim=(3, 5), dtype=torch.int32)
+    c = cp.reshape(-1, P, Hb, B, Wb, B).sum(dim=(3, 5), dtype=torch.int32)
+    m = torch.div(2 * S + c, 2 * c.clamp(min=1), rounding_mode="floor")
+    sat = (c > 0) & ((m > ROIBIN_CODE_MAX) | (m < -ROIBIN_CODE_MAX))
+    codes = torch.where(c > 0, m.clamp(-ROIBIN_CODE_MAX, ROIBIN_CODE_MAX),
+                        torch.full_like(m, ROIBIN_CODE_NONE)).to(torch.int16)
+    nsat = np.zeros(F, dtype=np.int32)
+    nsat[kf] = sat.sum(dim=(1, 2, 3)).numpy()
+
+    # boxes
+    nbox = np.zeros(F, dtype=np.int32)
+    nbad = np.zeros(F, dtype=np.int32)
+    flags = np.where(kept, 0, ROIBIN_FLAG_SKIPPED).astype(np.uint8)
+    flags[over] |= ROIBIN_FLAG_OVERFLOW
+    Wn = 2 * R + 1
+    xbits = x.numpy().view(np.uint32)
+    ctrs, recs, boxes = [], [], []
+    for f in range(F):
+        if not kept[f] or over[f]:
+            continue
+        rec = pk[f, :int(npk[f])].numpy()
+        valid, ctr = roibin_valid_records(rec, (P, H, W))
+        nbad[f] = int((~valid).sum())
+        if nbad[f]:
+            flags[f] |= ROIBIN_FLAG_BAD
+        slots = np.nonzero(valid)[0]
+        slots = slots[np.argsort(ctr[slots], kind="stable")]   # ties by slot
+        nbox[f] = len(slots)
+        for s in slots.tolist():
+            cc = int(ctr[s])
+            p, y, xx = cc // (H * W), (cc // W) % H, cc % W
+            b = np.full((Wn, Wn), ROIBIN_NAN_BITS, dtype=np.uint32)
+            y0, y1, x0, x1 = max(y - R, 0), min(y + R + 1, H), max(xx - R, 0), min(xx + R + 1, W)
+            b[y0 - (y - R):y1 - (y - R), x0 - (xx - R):x1 - (xx - R)] = xbits[f, p, y0:y1, x0:x1]
+            ctrs.append(cc)
+            recs.append(rec[s].view(np.uint32).copy())
+            boxes.append(b)
+    offs = np.zeros(F + 1, dtype=np.int64)
+    offs[1:] = np.cumsum(nbox)
+    K = len(ctrs)
+    rec_a = (np.stack(recs) if K else np.zeros((0, 8), np.uint32)).view(np.float32)
+    box_a = (np.stack(boxes) if K else np.zeros((0, Wn, Wn), np.uint32)).view(np.float32)
+    return RoibinBatch(torch.from_numpy(npk.astype(np.int32)), torch.from_numpy(nbox), torch.from_numpy(nbad),
+                       torch.from_numpy(nsat), torch.from_numpy(flags), torch.from_numpy(offs),
+                       torch.from_numpy(np.asarray(ctrs, dtype=np.int32)), torch.from_numpy(rec_a),
+                       torch.from_numpy(box_a), codes)

@@ -1074,10 +1074,10 @@ class DarkStatsConsumer(_RunAccumulator):
 
 
 class _PackedRows(_BatchConsumer):
-    """What the engines with packed per-frame rows share (sparse, droplets): the rows of a batch's
-    frames lie behind each other in the data columns, at most ``cap`` per frame, and reach the host
-    through pinned buffers in two steps per batch -- the header row first, then exactly ``offs[n]``
-    elements of every column.  Finished batches collect in :attr:`results` as the subclass's frame
+    """What the engines with packed per-frame rows share (sparse, droplets, roibin): the rows of a
+    batch's frames lie behind each other in the data columns, at most ``cap`` per frame, and reach the
+    host through pinned buffers in two steps per batch -- the header row first, then exactly ``offs[n]``
+    rows of every column (a row is ``_WIDTH[name]`` elements, one unless stated).  Finished batches collect in :attr:`results` as the subclass's frame
     objects (:meth:`take_results` hands them over).  The ring slots are released stream-ordered
     after the kernels, not after the copies.
 
@@ -1086,23 +1086,27 @@ class _PackedRows(_BatchConsumer):
         (``keep = 1`` while polling: after the NEXT batch, on the other stream, is in flight);
       * its data copy is issued on the batch's OWN stream -- behind the kernels that wrote the rows,
         ahead of the launch that reuses them (:meth:`_next`) -- for exactly ``offs[n]`` elements,
-        never the full capacity;
+        never the full capacity; what a subclass copies besides the columns (:meth:`_extra_copies`: rows
+        counted by something other than ``offs``) is issued at the same place, under the same rule;
       * it is collected one step later, when another batch is behind it;
       * :meth:`synchronize` flushes with two ``keep = 0`` passes: the first issues the last data
         copies, the second collects them.
 
     A subclass states ``_HDR``, the per-frame header fields ``(name, dtype name)`` -- header row b is
-    ``offs`` int64 [B + 1], then every field [B], padded to 16 B -- and ``_COLS``, the data columns,
-    sets ``cap`` and calls :meth:`_build_rows` once its batch is final."""
+    ``offs`` int64 [B + 1], then every field [B], padded to 16 B -- and ``_COLS``, the data columns
+    (``_WIDTH``: elements per row of a column that has more than one), sets ``cap`` and calls
+    :meth:`_build_rows` once its batch is final."""
 
     wants_meta = True
     meta_fields = 4
     _HDR = ()
     _COLS = ()
+    _WIDTH = {}
 
     def __init__(self, endpoint: QueueEndpoint, batch: Optional[int], ranks_per_gpu: Optional[int], streams: int,
                  stream_kind: str):
         super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        self._WIDTH = dict(self._WIDTH)
         self.results = []      # finished batches (frame objects), oldest first
         self._pending = collections.deque()   # GPU batches in flight: dicts, oldest first
         self._lock = threading.Lock()
@@ -1119,8 +1123,8 @@ class _PackedRows(_BatchConsumer):
         self._hdr_bytes = o
         self._hdr = torch.zeros((self._nbuf, (o + 15) // 16 * 16), dtype=torch.uint8, device=dev)
         self._hdr_host = torch.zeros(self._hdr.shape, dtype=torch.uint8, pin_memory=True)
-        self._out = {k: torch.empty((self._nbuf, B * self.cap), dtype=getattr(torch, dt), device=dev)
-                     for k, dt in self._COLS}
+        self._out = {k: torch.empty((self._nbuf, B * self.cap * self._WIDTH.get(k, 1)), dtype=getattr(torch, dt),
+                                    device=dev) for k, dt in self._COLS}
         self._scratch = [torch.empty(scratch_bytes, dtype=torch.uint8, device=dev) for _ in self.streams]
 
     def _split(self, row, n: int) -> dict:
@@ -1162,13 +1166,14 @@ class _PackedRows(_BatchConsumer):
                 p["hdr"].synchronize()
                 p["head"] = {k: v.copy() for k, v in self._split(self._hdr_host[p["b"]].numpy(), p["n"]).items()}
                 total = int(p["head"]["offs"][p["n"]])
-                p["cols"] = {k: torch.empty(total, dtype=getattr(torch, dt), pin_memory=total > 0)
-                             for k, dt in self._COLS}
+                p["cols"] = {k: torch.empty(total * self._WIDTH.get(k, 1), dtype=getattr(torch, dt),
+                                            pin_memory=total > 0) for k, dt in self._COLS}
                 ev = torch.cuda.Event()
-                with torch.cuda.stream(p["st"]):   # exactly offs[n] elements, never the full capacity
+                with torch.cuda.stream(p["st"]):   # exactly offs[n] rows, never the full capacity
                     if total:
                         for k, h in p["cols"].items():
-                            h.copy_(self._out[k][p["b"], :total], non_blocking=True)
+                            h.copy_(self._out[k][p["b"], :h.numel()], non_blocking=True)
+                    p["cols"].update(self._extra_copies(p["b"], p["n"], p["head"]))
                     ev.record(p["st"])
                 p["data"] = ev
         while self._pending and self._pending[0]["data"] is not None and len(self._pending) > 2 * keep:
@@ -1197,6 +1202,12 @@ class _PackedRows(_BatchConsumer):
 
     def _count(self, fr):
         """Add a finished batch to the counters behind :meth:`metrics` (the lock is held)."""
+
+    def _extra_copies(self, b: int, n: int, head: dict) -> dict:
+        """Data step of buffer row b (the batch's stream is current, its header ``head`` is on the host): issue
+        the copies of what the columns do not hold and return the pinned host tensors by name; they reach
+        :meth:`_frames_of` with the columns."""
+        return {}
 
 
 class SparseFrameConsumer(_PackedRows):
@@ -1853,3 +1864,146 @@ class CubeConsumer(_RunAccumulator):
                          self.nbins, bg.edges, bg.table_sha256, h["frames"].copy(), self.dropped, h["cnt"].copy(),
                          h["sum"].copy(), h["sq"].copy(), **self._meta_columns([m for ms, _ in self.rows for m in ms]),
                          bin=bins.astype(np.int16))
+
+
+class RoibinConsumer(_PackedRows):
+    """Consumer engine: batches of leased slots -> K-07 peak finder -> K-17 roibin (csrc/roibin.hip) ->
+    stream-ordered release.
+
+    Per kept frame (``counts >= min_peaks``): one lossless (2R+1)^2 box per peak record, ordered by centre, and the
+    frame binned ``bin`` x ``bin`` into int16 codes of ``step``.  The peak finder always runs (the boxes need its
+    records); its counts gate the frames ON THE DEVICE.  The boxes travel as packed rows the way
+    :class:`_PackedRows` states; the codes of the KEPT frames only follow in the same data step (a skipped frame's
+    code rows are neither written nor copied).  The batches reach :attr:`results` as
+    :class:`psana_ray_amd.roibin.RoibinFrames`."""
+
+    name = "roibin"
+    _HDR = (("npk", "int32"), ("nbox", "int32"), ("nbad", "int32"), ("nsat", "int32"), ("flags", "uint8"))
+    _COLS = (("ctr", "int32"), ("rec", "float32"), ("box", "float32"))
+
+    def __init__(self, endpoint: QueueEndpoint, frame_shape, bin: Optional[int] = None, step: Optional[float] = None,
+                 vmin: Optional[float] = None, vmax: Optional[float] = None, radius: Optional[int] = None, mask=None,
+                 min_peaks: int = 0, peak_params: Optional[PeakFinderParams] = None, detector: str = "",
+                 layout: str = "calib", batch: Optional[int] = None, stream_kind: str = CONSUMER_STREAM_KIND,
+                 streams: int = CONSUMER_STREAMS, ranks_per_gpu: Optional[int] = None, check_ring: bool = True):
+        """frame_shape: the shape of a (calibrated) frame, [P, H, W] or [H, W].  check_ring=False: the ring holds
+        RAW frames that the caller calibrates before :meth:`process_frames` (``--calibrate_on_read``)."""
+        from . import roibin as _roibin
+        from .ops import reference as R
+
+        super().__init__(endpoint, batch, ranks_per_gpu, streams, stream_kind)
+        self.shape = tuple(int(s) for s in frame_shape)
+        self.shape3 = R.photon_shape(self.shape, "roibin")
+        self.n = int(np.prod(self.shape3))
+        self.peak_params = peak_params or PeakFinderParams()
+        if self.peak_params.radius not in (1, 2):
+            raise ValueError("roibin: peak finder radius must be 1 or 2")
+        self.params = R.validate_roibin_params(
+            R.ROIBIN_BIN if bin is None else bin, R.ROIBIN_STEP if step is None else step,
+            R.ROIBIN_VMIN if vmin is None else vmin, R.ROIBIN_VMAX if vmax is None else vmax,
+            R.ROIBIN_RADIUS if radius is None else radius, self.peak_params.max_peaks, min_peaks, "roibin")
+        self.min_peaks = self.params.min_peaks
+        self.cap = self.params.max_peaks
+        self.code_shape = R.roibin_code_shape(self.shape3, self.params.bin)
+        self.frame_bytes = R.roibin_frame_bytes(self.shape3, self.params)
+        self._wn = 2 * self.params.radius + 1
+        self._WIDTH.update(rec=8, box=self._wn * self._wn)
+        self.detector, self.layout = str(detector), str(layout)
+        if check_ring:
+            self._check_ring(endpoint, "roibin needs calibrated float32 ones")
+        self._mask_np = None
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.dtype != np.uint8 or m.size != self.n or (m.ndim > 1 and tuple(m.shape) != self.shape):
+                raise ValueError(f"roibin: the mask must be uint8 of the frame's shape {self.shape}, got {m.dtype} "
+                                 f"{tuple(m.shape)}")
+            self._mask_np = np.ascontiguousarray(m.reshape(-1))
+        self.mask_sha256 = _roibin.mask_sha256(self._mask_np)
+        self.frames_kept = self.frames_skipped = self.frames_overflowed = self.boxes = self.saturated = 0
+        if self.gpu:
+            self._build_rows(0)
+            self._codes = torch.empty((self._nbuf, self.batch, *self.code_shape), dtype=torch.int16, device=self.device)
+            self._mask = None if self._mask_np is None else torch.from_numpy(self._mask_np).to(self.device)
+            self._pf = _PeakBuffers(self.device, self.peak_params, self.shape3, self.batch, self._nbuf,
+                                    len(self.streams))
+
+    def peak_dict(self) -> dict:
+        p = self.peak_params
+        return {"thr_peak": float(p.thr_peak), "son_min": float(p.son_min), "radius": float(p.radius)}
+
+    def _frames_of(self, meta, hdr, cols):
+        from .roibin import FLAG_SKIPPED, RoibinFrames
+
+        p = self.params
+        kept = (np.asarray(hdr["flags"]) & FLAG_SKIPPED) == 0
+        codes = cols.get("codes")
+        return RoibinFrames(self.detector, self.layout, self.shape, p.bin, p.step, p.inv, p.vmin, p.vmax, p.radius,
+                            p.max_peaks, p.min_peaks, self.peak_dict(), self.mask_sha256, **self._meta_columns(meta),
+                            **hdr, ctr=cols["ctr"], rec=np.asarray(cols["rec"]).reshape(-1, 8),
+                            box=np.asarray(cols["box"]).reshape(-1, self._wn, self._wn),
+                            koffs=np.concatenate([[0], np.cumsum(kept)]).astype(np.int64),
+                            codes=None if codes is None else np.asarray(codes).reshape(-1, *self.code_shape))
+
+    def _count(self, rf):
+        from .roibin import FLAG_OVERFLOW, FLAG_SKIPPED
+
+        self.frames_skipped += int(((rf.flags & FLAG_SKIPPED) != 0).sum())
+        self.frames_overflowed += int(((rf.flags & FLAG_OVERFLOW) != 0).sum())
+        self.frames_kept += int(rf.koffs[-1])
+        self.boxes += int(rf.offs[-1])
+        self.saturated += int(rf.nsat.astype(np.int64).sum())
+
+    def _extra_copies(self, b, n, head):
+        """The code rows of the batch's KEPT frames, run by run: a skipped frame's codes never cross to the host."""
+        kept = (head["flags"] & 2) == 0
+        K = int(kept.sum())
+        host = torch.empty((K, *self.code_shape), dtype=torch.int16, pin_memory=K > 0)
+        edges = np.flatnonzero(np.diff(np.concatenate([[0], kept.astype(np.int8), [0]])))   # run starts and ends
+        j = 0
+        for a, e in zip(edges[::2].tolist(), edges[1::2].tolist()):
+            host[j:j + e - a].copy_(self._codes[b, a:e], non_blocking=True)
+            j += e - a
+        return {"codes": host}
+
+    def _launch_slots(self, C, slots, b, k, st):
+        n = len(slots)
+        h, o, p = self._split(self._hdr[b], n), self._out, self.params
+        P, H, W = self.shape3
+        self._pf.launch_slots(C, self.ep, slots, b, k, st)
+        C.roibin_slots(self.ep.pool, self.ep._slot_bytes, slots, P, H, W, p.bin, p.inv, p.vmin, p.vmax, p.radius,
+                       p.min_peaks, p.max_peaks, 0 if self._mask is None else int(self._mask.data_ptr()),
+                       int(self._pf.peaks[b].data_ptr()), int(self._pf.counts[b].data_ptr()),
+                       int(self._codes[b].data_ptr()), int(h["npk"].data_ptr()), int(h["nbox"].data_ptr()),
+                       int(h["nbad"].data_ptr()), int(h["nsat"].data_ptr()), int(h["flags"].data_ptr()),
+                       int(h["offs"].data_ptr()), int(o["ctr"][b].data_ptr()), int(o["rec"][b].data_ptr()),
+                       int(o["box"][b].data_ptr()), int(st.cuda_stream))
+
+    def _launch_tensors(self, frames, b, k, st):
+        n = len(frames)
+        h, o, p = self._split(self._hdr[b], n), self._out, self.params
+        rows = n * p.max_peaks
+        self._pf.launch_tensors([t.reshape(-1) for t in frames], b, k, st)
+        kernels.roibin([t.reshape(-1) for t in frames], self.shape3, p, self._pf.peaks[b, :n], self._pf.counts[b, :n],
+                       self._codes[b, :n], h["npk"], h["nbox"], h["nbad"], h["nsat"], h["flags"], h["offs"],
+                       o["ctr"][b, :rows], o["rec"][b, :rows * 8].view(rows, 8),
+                       o["box"][b, :rows * self._wn ** 2].view(rows, self._wn, self._wn), mask=self._mask, stream=st)
+
+    def _reference(self, frames, meta):
+        from .ops import reference
+
+        p = self.params
+        x = torch.stack([t.reshape(self.shape3) for t in frames]).to(torch.float32)
+        found, _summary = reference.peakfind_reference(x, self.peak_params)
+        peaks = torch.zeros((len(frames), p.max_peaks, 8), dtype=torch.float32)
+        for f, rec in enumerate(found):
+            peaks[f, :min(rec.shape[0], p.max_peaks)] = rec[:p.max_peaks]
+        counts = torch.tensor([int(r.shape[0]) for r in found], dtype=torch.int32)
+        g = reference.roibin_reference(x, self.shape3, peaks, counts, p, mask=self._mask_np)
+        self._collect(self._frames_of(meta, {k: getattr(g, k).numpy() for k in ("offs", "npk", "nbox", "nbad", "nsat",
+                                                                                "flags")},
+                                      {"ctr": g.ctr.numpy(), "rec": g.rec.numpy(), "box": g.box.numpy(),
+                                       "codes": g.codes.numpy()}))
+
+    def metrics(self) -> dict:
+        return {"frames_consumed": self.frames, "frames_kept": self.frames_kept, "frames_skipped": self.frames_skipped,
+                "frames_overflowed": self.frames_overflowed, "boxes": self.boxes, "saturated": self.saturated}

@@ -77,7 +77,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--data_dir", type=str, default=None, help="raw-run files directory (or $PSANA_RAY_DATA)")
     g.add_argument("--chunk", type=int, default=64, help="frames per H2D copy / kernel launch (<= 64)")
     g.add_argument("--route", type=str, default="balanced", choices=["balanced", "local_first", "spread"])
-    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets", "cube", "roi"],
+    g.add_argument("--consumer_task", type=str, default="none", choices=["none", "peakfind", "radial", "dark", "sparse", "powder", "hist", "photons", "droplets", "cube", "roi", "roibin"],
                    help="also consume on every producer rank (co-located consumer, BASELINE config 5): the K-07 "
                         "peak finder, the K-08 radial profile (default binning of psana-ray-consumer), the K-09 "
                         "dark statistics (needs --mode raw; --out_dark writes the file), or the K-10 zero "
@@ -91,7 +91,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "psana-ray-consumer --task droplets), or the K-15 cube (--out_cube writes the file; "
                         "--cube_by ... --cube_frac_bits as for psana-ray-consumer --task cube), or the K-16 ROI "
                         "statistics (--out_roi writes the file; --roi ... --roi_mask as for psana-ray-consumer --task "
-                        "roi)")
+                        "roi), or the K-17 roibin (--out_roibin writes the file; --rb_bin ... --rb_mask, --min_peaks as "
+                        "for psana-ray-consumer --task roibin)")
+    g.add_argument("--out_roibin", type=str, default=None,
+                   help="--consumer_task roibin: write the rank's peak boxes and binned codes "
+                        "(psana_ray_amd.roibin.RoibinFrames .npz) here")
     g.add_argument("--out_roi", type=str, default=None,
                    help="--consumer_task roi: write the rank's per-frame ROI records (psana_ray_amd.roi.RoiFrames .npz) "
                         "here")
@@ -141,7 +145,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--local", action="store_true",
                    help="single-process queue: no rendezvous; requires --consumer_task (no external consumers)")
     from .consumer import (add_cube_arguments, add_droplet_arguments, add_hist_arguments, add_photon_arguments,
-                           add_powder_arguments, add_roi_arguments, add_sparse_arguments)
+                           add_powder_arguments, add_roi_arguments, add_roibin_arguments, add_sparse_arguments)
 
     add_sparse_arguments(parser)
     add_powder_arguments(parser)
@@ -150,6 +154,7 @@ def build_parser() -> argparse.ArgumentParser:
     add_droplet_arguments(parser)
     add_cube_arguments(parser)
     add_roi_arguments(parser)
+    add_roibin_arguments(parser)
     return parser
 
 
@@ -313,7 +318,7 @@ def main(argv=None) -> int:
                       "or a co-located --consumer_task")
             return 2
         mode = Mode.raw   # frames travel raw; DataReader applies read_mode
-    if args.consumer_task in ("radial", "sparse", "powder", "hist", "photons", "droplets", "cube", "roi") and (mode == Mode.raw or int(args.panel_shards) > 1):
+    if args.consumer_task in ("radial", "sparse", "powder", "hist", "photons", "droplets", "cube", "roi", "roibin") and (mode == Mode.raw or int(args.panel_shards) > 1):
         log.error("--consumer_task %s needs whole calibrated frames (not --mode raw / --panel_shards)",
                   args.consumer_task)
         return 2
@@ -322,7 +327,7 @@ def main(argv=None) -> int:
         return 2
     for flag, task in (("out_sparse", "sparse"), ("out_dark", "dark"), ("out_powder", "powder"),
                        ("out_hist", "hist"), ("out_photons", "photons"), ("out_droplets", "droplets"), ("out_cube", "cube"),
-                       ("out_roi", "roi")):
+                       ("out_roi", "roi"), ("out_roibin", "roibin")):
         if getattr(args, flag) is not None and args.consumer_task != task:
             log.error("--%s belongs to --consumer_task %s", flag, task)
             return 2
@@ -469,7 +474,7 @@ def main(argv=None) -> int:
             # consumer thread, at the end of the stream), report(result or None, frames consumed) after the join
             each = None
 
-            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder / .hist / .photons / .droplets / .cube / .roi merge)
+            def rank_path(path):   # one file per rank (they merge: python -m psana_ray_amd.dark / .sparse / .powder / .hist / .photons / .droplets / .cube / .roi / .roibin merge)
                 root, ext = os.path.splitext(path)
                 return path if size == 1 else f"{root}.r{rank}{ext}"
 
@@ -639,6 +644,33 @@ def main(argv=None) -> int:
                         path = rank_path(args.out_roi)
                         rf.save(path)
                         log.info("Rank %d: ROI records written to %s", rank, path)
+            elif args.consumer_task == "roibin":
+                try:
+                    from . import roibin as _roibin
+                    from .consumer import roibin_consumer, roibin_final_line, roibin_start_line
+
+                    args.batch = None   # config.pipeline_shape, as for the other co-located consumers
+                    cons = roibin_consumer(args, ep, frame_shape, args.detector_name, mode.value)
+                except (ValueError, OSError) as e:
+                    log.error("--consumer_task roibin: %s", e)
+                    return 2
+                print(roibin_start_line(rank, cons), flush=True)
+                rwriter = SparseWriter(args.out_roibin and rank_path(args.out_roibin), args.part_frames,
+                                       concat=_roibin.concat)
+
+                def each():
+                    rwriter.add(cons.take_results())
+
+                def finish():
+                    cons.synchronize()
+                    each()
+                    rwriter.close(cons.empty())
+                    return cons.metrics()
+
+                def report(m, consumed):
+                    print(roibin_final_line(rank, cons), flush=True)
+                    if rwriter.paths:
+                        log.info("Rank %d: roibin frames written to %s", rank, ", ".join(rwriter.paths))
             else:
                 cons = PeakFinderConsumer(ep, frame_shape, PeakFinderParams())
                 finish = cons.synchronize
