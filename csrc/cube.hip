@@ -16,16 +16,13 @@
 // 2^31 and a run at or below min(2^31 - 1, (2^63 - 1) / Q^2) frames, so no word overflows.  The kernel
 // never clears anything.
 //
-// MI355X design: powder_kernel's lane (4 consecutive pixels, one 16-B non-temporal load per frame, one
-// owner per pixel per launch, so no atomics; scalar tail lane for n % 4; planes b >= 1 word by word when
-// n % 4 != 0, since they are then not 16-B aligned), with the two ballot-built class masks replaced by
-// a PLAN the launcher makes on the host and passes BY VALUE in the kernel arguments (CubePlan, about 1
-// KB): the kept frames' addresses sorted into GROUPS of equal bin (the groups in the order their bins
+// MI355X design: the owner-lane accumulator of accum.h over 16-B float32 loads, one plane per bin, fed
+// by a PLAN the launcher makes on the host and passes BY VALUE in the kernel arguments (CubePlan, about
+// 1 KB): the kept frames' addresses sorted into GROUPS of equal bin (the groups in the order their bins
 // first appear, a group's frames in batch order), the end of every group and its bin.  The sorted
 // addresses ARE the frame order: the kernel needs no index of a frame.  All control flow over groups is
-// scalar; addresses, ends and bins come by scalar loads.  Per group: one pass over its frames with 8,
-// then 4, then 1 loads in flight, ONE set of partials in registers, then ONE 16-B read-modify-write of
-// the lane's words of plane b (cnt: one access, sum / sq: two each).
+// scalar; addresses, ends and bins come by scalar loads.  Per group: one pass over its frames, ONE set
+// of partials in registers, then the read-modify-write of the lane's words of plane b.
 //
 // Single-frame groups (a delay scan with jitter puts nearly every frame of a batch into another bin, G
 // close to F) were ALSO built four -- and two -- at a time, the frame loads and the twenty accumulator
@@ -52,14 +49,11 @@
 // cube_kernel: 94 VGPRs, 106 SGPRs, no scratch memory (0 bytes per lane, no VGPR spills; 22 scalar
 // registers parked in vector-register lanes), no LDS, occupancy 5 waves per SIMD.  The frame addresses
 // come by s_load_dwordx2, the frames by global_load_dwordx4 nt, no flat access.
-#include <cmath>
-
-#include "common.h"
+#include "accum.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace pr {
-
-typedef unsigned long long cube_u64x2_t __attribute__((ext_vector_type(2)));
 
 struct CubeParams {
   float vmin, vmax, scale;   // scale = 2^S
@@ -110,56 +104,6 @@ __device__ __forceinline__ void cube_add4(CubePart<4>& a, const f32x4_t r, const
   cube_add<4, 3>(a, r.w, pp);
 }
 
-// K frames from frame f on with K loads in flight
-template <int K>
-__device__ __forceinline__ void cube_frames(CubePart<4>& a, const CubePlan& pl, int& f, const int64_t q,
-                                            const CubeParams& pp) {
-  f32x4_t r[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) r[k] = ld_nt_f4(gin<f32x4_t>(pl.frame[f + k]) + q);
-#pragma unroll
-  for (int k = 0; k < K; ++k) cube_add4(a, r[k], pp);
-  f += K;
-}
-
-// a lane's words of one plane: 4 counts, 4 sums, 4 sums of squares
-struct CubeWords {
-  u32x4_t c;
-  cube_u64x2_t s0, s1, q0, q1;
-};
-
-__device__ __forceinline__ CubeWords cube_load(const int32_t* cnt, const long long* sum,
-                                               const unsigned long long* sq, const int64_t o) {
-  CubeWords w;
-  w.c = *reinterpret_cast<const u32x4_t*>(cnt + o);
-  const cube_u64x2_t* ps = reinterpret_cast<const cube_u64x2_t*>(sum + o);
-  const cube_u64x2_t* pq = reinterpret_cast<const cube_u64x2_t*>(sq + o);
-  w.s0 = ps[0];
-  w.s1 = ps[1];
-  w.q0 = pq[0];
-  w.q1 = pq[1];
-  return w;
-}
-
-__device__ __forceinline__ void cube_merge(CubeWords& w, const CubePart<4>& a) {
-  w.c.x += a.cnt[0]; w.c.y += a.cnt[1]; w.c.z += a.cnt[2]; w.c.w += a.cnt[3];
-  // two's complement: the unsigned 64-bit add of a signed partial is the signed add
-  w.s0.x += (unsigned long long)a.sum[0]; w.s0.y += (unsigned long long)a.sum[1];
-  w.s1.x += (unsigned long long)a.sum[2]; w.s1.y += (unsigned long long)a.sum[3];
-  w.q0.x += a.sq[0]; w.q0.y += a.sq[1]; w.q1.x += a.sq[2]; w.q1.y += a.sq[3];
-}
-
-__device__ __forceinline__ void cube_store(int32_t* cnt, long long* sum, unsigned long long* sq, const int64_t o,
-                                           const CubeWords& w) {
-  *reinterpret_cast<u32x4_t*>(cnt + o) = w.c;
-  cube_u64x2_t* ps = reinterpret_cast<cube_u64x2_t*>(sum + o);
-  cube_u64x2_t* pq = reinterpret_cast<cube_u64x2_t*>(sq + o);
-  ps[0] = w.s0;
-  ps[1] = w.s1;
-  pq[0] = w.q0;
-  pq[1] = w.q1;
-}
-
 __global__ __launch_bounds__(256) void cube_kernel(const CubePlan pl, const int64_t n, const CubeParams pp,
                                                    long long* __restrict__ nfr, int32_t* __restrict__ cnt,
                                                    long long* __restrict__ sum,
@@ -182,25 +126,17 @@ __global__ __launch_bounds__(256) void cube_kernel(const CubePlan pl, const int6
       const int b = pl.gbin[g];
       CubePart<4> a;
       cube_zero(a);
-      int left = pl.gend[g] - f;
-      for (; left >= 8; left -= 8) cube_frames<8>(a, pl, f, q, pp);
-      if (left >= 4) {
-        cube_frames<4>(a, pl, f, q, pp);
-        left -= 4;
-      }
-      for (; left > 0; --left) cube_frames<1>(a, pl, f, q, pp);
+      acc_group<f32x4_t, true>(pl.gend[g] - f, q, [&] { return pl.frame[f++]; },
+                               [&](const f32x4_t r) { cube_add4(a, r, pp); });
       const int64_t o = (int64_t)b * n + p0;
       if (vec || b == 0) {
-        CubeWords w = cube_load(cnt, sum, sq, o);
-        cube_merge(w, a);
-        cube_store(cnt, sum, sq, o, w);
+        Words32 wc;
+        Words64 ws, wq;
+        wc.load(cnt + o); ws.load(sum + o); wq.load(sq + o);
+        wc.add(a.cnt); ws.add(a.sum); wq.add(a.sq);
+        wc.store(cnt + o); ws.store(sum + o); wq.store(sq + o);
       } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          cnt[o + i] += (int32_t)a.cnt[i];
-          sum[o + i] += a.sum[i];
-          sq[o + i] += a.sq[i];
-        }
+        acc_add(cnt + o, a.cnt); acc_add(sum + o, a.sum); acc_add(sq + o, a.sq);
       }
     }
   } else if (q == nq) {
@@ -213,9 +149,7 @@ __global__ __launch_bounds__(256) void cube_kernel(const CubePlan pl, const int6
         const int end = pl.gend[g];
         for (; f < end; ++f) cube_add<1, 0>(a, gin<float>(pl.frame[f])[p], pp);
         const int64_t o = (int64_t)pl.gbin[g] * n + p;
-        cnt[o] += (int32_t)a.cnt[0];
-        sum[o] += a.sum[0];
-        sq[o] += a.sq[0];
+        acc_add(cnt + o, a.cnt); acc_add(sum + o, a.sum); acc_add(sq + o, a.sq);
       }
     }
   }
@@ -223,22 +157,16 @@ __global__ __launch_bounds__(256) void cube_kernel(const CubePlan pl, const int6
 
 void launch_cube(const FramePtrs& fp, int nframes, int64_t n, float vmin, float vmax, int frac_bits, int nbins,
                  const int32_t* bins, uint64_t nfr, uint64_t cnt, uint64_t sum, uint64_t sq, uint64_t stream) {
-  check(nframes >= 1 && nframes <= kMaxFrames, "cube: nframes out of range");
-  check(n >= 1 && n < (int64_t)1 << 31, "cube: frame size out of range");
-  check(std::isfinite(vmin) && std::isfinite(vmax) && vmin <= vmax, "cube: the value window must be finite and ordered");
-  check(frac_bits >= 0 && frac_bits <= 16, "cube: frac_bits outside [0, 16]");
-  // Q = ceil(max(|vmin|, |vmax|) * 2^S) in doubles: a float32 times 2^16 is exact
-  const double Q = std::ceil(std::ldexp(std::max(std::fabs((double)vmin), std::fabs((double)vmax)), frac_bits));
-  check(Q < 2147483648.0, "cube: max(|vmin|, |vmax|) * 2^frac_bits must stay below 2^31");
-  const unsigned __int128 q2 = (unsigned __int128)(uint64_t)Q * (uint64_t)Q;
-  check(q2 * (unsigned)nframes <= (unsigned __int128)INT64_MAX, "cube: more frames than (2^63 - 1) / Q^2");
+  check_nframes(nframes, "cube");
+  check_frame_size(n, "cube");
+  const CubeParams pp{vmin, vmax, quant_bound(vmin, vmax, frac_bits, nframes, "cube")};
   check(nbins >= 1 && nbins <= kCubeMaxBins, "cube: nbins outside [1, 4096]");
   check(bins != nullptr, "cube: no bins");
   check(nfr != 0 && nfr % 8 == 0, "cube: nfr must be non-null and 8-B aligned");
   check(cnt != 0 && sum != 0 && sq != 0 && aligned16(cnt) && aligned16(sum) && aligned16(sq),
         "cube: accumulators must be non-null and 16-B aligned");
   for (int f = 0; f < nframes; ++f) {
-    check(fp.in[f] != 0 && aligned16(fp.in[f]), "cube: frames must be 16-B aligned");
+    check_frame(fp.in[f], "cube");
     check(bins[f] >= -1 && bins[f] < nbins, "cube: a frame's bin is outside -1 .. nbins - 1");
   }
   // the plan: the groups in the order their bins first appear, a group's frames in batch order (stable)
@@ -257,10 +185,7 @@ void launch_cube(const FramePtrs& fp, int nframes, int64_t n, float vmin, float 
     ++pl.ngroups;
   }
   if (pl.ngroups == 0) return;   // every frame dropped: nothing is launched, nothing is written
-  const int64_t lanes = n / 4 + (n % 4 != 0 ? 1 : 0);
-  const dim3 grid((unsigned)((lanes + 255) / 256));
-  const CubeParams pp{vmin, vmax, std::ldexp(1.0f, frac_bits)};
-  hipLaunchKernelGGL(cube_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pl, n, pp,
+  hipLaunchKernelGGL(cube_kernel, owner_lane_grid(n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pl, n, pp,
                      reinterpret_cast<long long*>(nfr), reinterpret_cast<int32_t*>(cnt),
                      reinterpret_cast<long long*>(sum), reinterpret_cast<unsigned long long*>(sq));
   hip_check(hipGetLastError(), "cube launch");

@@ -13,18 +13,14 @@
 // 65535^2 * (2^31 - 1) < 2^63: the only limit is the int32 count, which the callers hold below 2^31
 // frames per run.  The kernel never clears the accumulators.
 //
-// MI355X design: a lane owns 4 consecutive pixels (one 8-B non-temporal raw load per frame, like
-// calib_basic4_kernel), loops over the batch's frames with 8 loads in flight and keeps its partials
-// in registers -- one owner per pixel per launch, so no atomics.  In-batch partials are 32-bit where
-// the 64-frame bound proves it (cnt <= 64, sum <= 64 * 65535 < 2^32); sq (64 * 65535^2 > 2^32) is
-// 64-bit.  After the frame loop ONE read-modify-write of the lane's accumulator words: planar per
-// quantity and candidate, 16-B accesses (cnt: one, sum / sq: two each).  A candidate none of the
-// lane's four pixels hit is skipped -- its words are neither read nor written (an epix dark run never
-// hits candidate 1: half the accumulator traffic).  The n % 4 last pixels of a frame go to one extra
-// lane that walks them one by one with scalar accesses; so do all pixels of candidates c >= 1 when
-// n % 4 != 0 (their planes are then not 16-B aligned).
-#include "common.h"
+// MI355X design: the owner-lane accumulator of accum.h over 8-B raw loads, 8 then 1 loads in flight,
+// one plane per candidate.  In-batch partials are 32-bit where the 64-frame bound proves it (cnt <= 64,
+// sum <= 64 * 65535 < 2^32); sq (64 * 65535^2 > 2^32) is 64-bit.  A candidate none of the lane's four
+// pixels hit is skipped -- its words are neither read nor written (an epix dark run never hits
+// candidate 1: half the accumulator traffic).
+#include "accum.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace pr {
 
@@ -36,8 +32,6 @@ template <>
 struct DarkTraits<kJungfrau> { static constexpr int NC = 3; };
 template <>
 struct DarkTraits<kPlain> { static constexpr int NC = 1; };
-
-typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
 
 // in-batch partials of NP pixels; every index is a compile-time constant after unrolling, so the
 // arrays live in VGPRs (a candidate-indexed access would send them to scratch)
@@ -98,14 +92,8 @@ __global__ __launch_bounds__(256) void dark_kernel(const FramePtrs fp, const int
     DarkPart<NC, 4> a;
     dark_zero(a);
     int f = 0;
-    for (; f + 8 <= nframes; f += 8) {
-      uint2 r[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) r[k] = ld_nt_u2(gin<uint2>(fp.in[f + k]) + q);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) dark_add4<KIND, NC>(a, r[k], lo, span);
-    }
-    for (; f < nframes; ++f) dark_add4<KIND, NC>(a, ld_nt_u2(gin<uint2>(fp.in[f]) + q), lo, span);
+    acc_group<uint2, false>(nframes, q, [&] { return fp.in[f++]; },
+                            [&](const uint2 r) { dark_add4<KIND, NC>(a, r, lo, span); });
     const int64_t p0 = q * 4;
     const bool vec = (n & 3) == 0;   // planes of c >= 1 start at c * n: 16-B aligned iff n % 4 == 0
 #pragma unroll
@@ -113,25 +101,13 @@ __global__ __launch_bounds__(256) void dark_kernel(const FramePtrs fp, const int
       if ((a.cnt[c][0] | a.cnt[c][1] | a.cnt[c][2] | a.cnt[c][3]) == 0u) continue;   // untouched: words stay as they are
       const int64_t o = (int64_t)c * n + p0;
       if (c == 0 || vec) {
-        u32x4_t* pc = reinterpret_cast<u32x4_t*>(cnt + o);
-        u32x4_t vc = *pc;
-        u64x2_t* ps = reinterpret_cast<u64x2_t*>(sum + o);
-        u64x2_t s0 = ps[0], s1 = ps[1];
-        u64x2_t* pq = reinterpret_cast<u64x2_t*>(sq + o);
-        u64x2_t q0 = pq[0], q1 = pq[1];
-        vc.x += a.cnt[c][0]; vc.y += a.cnt[c][1]; vc.z += a.cnt[c][2]; vc.w += a.cnt[c][3];
-        s0.x += a.sum[c][0]; s0.y += a.sum[c][1]; s1.x += a.sum[c][2]; s1.y += a.sum[c][3];
-        q0.x += a.sq[c][0]; q0.y += a.sq[c][1]; q1.x += a.sq[c][2]; q1.y += a.sq[c][3];
-        *pc = vc;
-        ps[0] = s0; ps[1] = s1;
-        pq[0] = q0; pq[1] = q1;
+        Words32 wc;
+        Words64 ws, wq;
+        wc.load(cnt + o); ws.load(sum + o); wq.load(sq + o);
+        wc.add(a.cnt[c]); ws.add(a.sum[c]); wq.add(a.sq[c]);
+        wc.store(cnt + o); ws.store(sum + o); wq.store(sq + o);
       } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          cnt[o + i] += (int32_t)a.cnt[c][i];
-          sum[o + i] += a.sum[c][i];
-          sq[o + i] += a.sq[c][i];
-        }
+        acc_add(cnt + o, a.cnt[c]); acc_add(sum + o, a.sum[c]); acc_add(sq + o, a.sq[c]);
       }
     }
   } else if (q == nq) {
@@ -144,9 +120,7 @@ __global__ __launch_bounds__(256) void dark_kernel(const FramePtrs fp, const int
       for (int c = 0; c < NC; ++c) {
         if (a.cnt[c][0] == 0u) continue;
         const int64_t o = (int64_t)c * n + p;
-        cnt[o] += (int32_t)a.cnt[c][0];
-        sum[o] += a.sum[c][0];
-        sq[o] += a.sq[c][0];
+        acc_add(cnt + o, a.cnt[c]); acc_add(sum + o, a.sum[c]); acc_add(sq + o, a.sq[c]);
       }
     }
   }
@@ -154,15 +128,14 @@ __global__ __launch_bounds__(256) void dark_kernel(const FramePtrs fp, const int
 
 void launch_dark(const FramePtrs& fp, int nframes, int64_t n, int kind, int adu_lo, int adu_hi, uint64_t cnt,
                  uint64_t sum, uint64_t sq, uint64_t stream) {
-  check(nframes >= 1 && nframes <= kMaxFrames, "dark: nframes out of range");
-  check(n >= 1 && n < (int64_t)1 << 31, "dark: frame size out of range");
+  check_nframes(nframes, "dark");
+  check_frame_size(n, "dark");
   check(kind >= 0 && kind <= 2, "dark: unknown gain kind");
   check(adu_lo >= 0 && adu_lo <= adu_hi && adu_hi <= 65535, "dark: the ADU window must satisfy 0 <= lo <= hi <= 65535");
   check(cnt != 0 && sum != 0 && sq != 0 && aligned16(cnt) && aligned16(sum) && aligned16(sq),
         "dark: accumulators must be non-null and 16-B aligned");
-  for (int f = 0; f < nframes; ++f) check(fp.in[f] != 0 && aligned16(fp.in[f]), "dark: frames must be 16-B aligned");
-  const int64_t lanes = n / 4 + (n % 4 != 0 ? 1 : 0);
-  const dim3 grid((unsigned)((lanes + 255) / 256));
+  check_frames(fp, nframes, "dark");
+  const dim3 grid = owner_lane_grid(n);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int32_t* C = reinterpret_cast<int32_t*>(cnt);
   unsigned long long* S = reinterpret_cast<unsigned long long*>(sum);

@@ -63,6 +63,7 @@
 // 1.88 / 0.81 / 6.04.  Not built: an in-wave combine of equal-root neighbours before the atomics.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -351,8 +352,8 @@ static int64_t dr_align16(int64_t x) { return (x + 15) / 16 * 16; }
 static int64_t dr_rows(int64_t cap_pix, int frames) { return (cap_pix * frames + 3) / 4 * 4; }
 
 int64_t droplets_scratch_bytes(int64_t n, int64_t cap_pix, int64_t cap, int frames) {
-  check(n >= 1 && n < (int64_t)1 << 31, "droplets: frame size out of range");
-  check(frames >= 1 && frames <= kMaxFrames, "droplets: nframes out of range");
+  check_frame_size(n, "droplets");
+  check_nframes(frames, "droplets");
   check(cap_pix >= 1 && cap_pix * frames < (int64_t)1 << 31, "droplets: cap_pix out of range");
   check(cap >= 1 && cap * frames < (int64_t)1 << 31, "droplets: cap out of range");
   return kDrHeader + kDrCntBytes + dr_align16(sparsify_scratch_bytes(n, cap_pix, frames)) +
@@ -364,7 +365,7 @@ void launch_droplets(const FramePtrs& fp, int nframes, int P, int H, int W, floa
                      uint64_t flags, uint64_t offs, uint64_t label, uint64_t npix, uint64_t adu, uint64_t sy, uint64_t sx,
                      uint64_t qmax, uint64_t scratch, int64_t scratch_bytes, uint64_t stream, int phases) {
   check(phases >= 1 && phases <= 15, "droplets: phases is a mask of 1 (scan), 2 (index + link), 4 (reduce), 8 (pack)");
-  check(nframes >= 1 && nframes <= kMaxFrames, "droplets: nframes out of range");
+  check_nframes(nframes, "droplets");
   check(P >= 1 && H >= 1 && W >= 1 && (int64_t)P * H * W < (int64_t)1 << 31, "droplets: shape out of range");
   const int64_t n = (int64_t)P * H * W, hw = (int64_t)H * W;
   check(cap_pix >= 1 && cap_pix * nframes < (int64_t)1 << 31, "droplets: cap_pix must be >= 1 and F * cap_pix < 2^31");
@@ -384,7 +385,7 @@ void launch_droplets(const FramePtrs& fp, int nframes, int P, int H, int W, floa
         "droplets: misaligned or missing output");
   check(scratch != 0 && scratch % 16 == 0, "droplets: the scratch block must be 16-B aligned");
   check(scratch_bytes >= droplets_scratch_bytes(n, cap_pix, cap, nframes), "droplets: scratch block too small");
-  for (int f = 0; f < nframes; ++f) check(fp.in[f] != 0 && aligned16(fp.in[f]), "droplets: frames must be 16-B aligned");
+  check_frames(fp, nframes, "droplets");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t rows = dr_rows(cap_pix, nframes);
   const int64_t sps = dr_align16(sparsify_scratch_bytes(n, cap_pix, nframes));

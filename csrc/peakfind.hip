@@ -29,9 +29,7 @@
 // the losing variants are retired).
 #include "common.h"
 #include "kernels.h"
-
-#include <map>
-#include <mutex>
+#include "launch.h"
 
 #include <algorithm>
 
@@ -515,36 +513,15 @@ __global__ __launch_bounds__(256) PR_PF_WAVES_ATTR void peakfind_range_kernel(co
   if (threadIdx.x == 0) atomicExch(&scratch->done, 0u);
 }
 
-// resident workgroups of a 256-thread kernel on the CURRENT device, queried once per (device,
-// kernel) under a lock: a process that drives several GPUs, or launches from several threads, sizes
-// every grid from its own device's answer (speed only: the last-workgroup protocol needs no
-// co-residency)
-template <typename Kern>
-static int pf_resident_blocks(int which, Kern k) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, int> cache;
-  int dev = 0;
-  hip_check(hipGetDevice(&dev), "pf device");
-  std::lock_guard<std::mutex> lk(mu);
-  int& n = cache[{dev, which}];
-  if (n == 0) {
-    int cus = 0, per = 0;
-    hip_check(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "pf cu count");
-    hip_check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)k, 256, 0), "pf occupancy");
-    n = std::max(1, cus * std::max(1, per));
-  }
-  return n;
-}
-
 void launch_peakfind(const FramePtrs& fp, int nframes, int n_panels, int rows, int cols, float thr_peak,
                      float son_min, int radius, int max_peaks, uint64_t peaks, uint64_t counts,
                      uint64_t summary, uint64_t total, uint64_t stream, uint64_t scratch) {
-  check(nframes >= 1 && nframes <= kMaxFrames, "peakfind: nframes out of range");
+  check_nframes(nframes, "peakfind");
   check(radius == 1 || radius == 2, "peakfind: radius must be 1 or 2");
   check(max_peaks >= 1, "peakfind: max_peaks must be >= 1");
   check(cols % 4 == 0, "peakfind: panel width must be a multiple of 4");
   check((int64_t)n_panels * rows * cols < (int64_t)1 << 31, "peakfind: frame too large for 32-bit pixel ids");
-  for (int f = 0; f < nframes; ++f) check(aligned16(fp.in[f]), "peakfind: frames must be 16-B aligned");
+  check_frames(fp, nframes, "peakfind", /*nonnull=*/false);
   PfParams pp{thr_peak, son_min, max_peaks, n_panels, rows, cols};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   float* P = reinterpret_cast<float*>(peaks);
@@ -557,7 +534,8 @@ void launch_peakfind(const FramePtrs& fp, int nframes, int n_panels, int rows, i
   const int64_t n4 = (int64_t)n_panels * rows * cols / 4;
   const int64_t chunks = (n4 + 256 * K - 1) / (256 * K) * nframes;
   auto kern = radius == 1 ? peakfind_range_kernel<1, K> : peakfind_range_kernel<2, K>;
-  const int g = (int)std::min<int64_t>(chunks, pf_resident_blocks(radius == 1 ? 0 : 1, kern));
+  // one resident wave of workgroups (speed only: the last-workgroup protocol needs no co-residency)
+  const int g = (int)std::min<int64_t>(chunks, resident_blocks((const void*)kern, 0, "pf"));
   const bool spill_ok = (int64_t)n_panels * rows * cols < ((int64_t)1 << kPfSpillShift) && nframes <= 64;
   hipLaunchKernelGGL(kern, dim3(g), dim3(256), 0, s, fp, pp, P, C, S, T, X, nframes, spill_ok);
   hip_check(hipGetLastError(), "peakfind launch");

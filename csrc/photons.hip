@@ -49,6 +49,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace pr {
 
@@ -262,7 +263,7 @@ int photons_max_grid() { return kPhotGrid; }
 void launch_photons(const FramePtrs& fp, int nframes, int P, int H, int W, float inv, float vmax, float thr_seed,
                     float thr_total, uint64_t mask, uint64_t roi, int n_roi, uint64_t kmap, uint64_t cnt,
                     uint64_t psum, uint64_t occ, uint64_t pk, uint64_t tot, uint64_t stream, int variant) {
-  check(nframes >= 1 && nframes <= kMaxFrames, "photons: nframes out of range");
+  check_nframes(nframes, "photons");
   check(P >= 1 && H >= 1 && W >= 1, "photons: the shape must be positive");
   const int64_t n = (int64_t)P * H * W;
   check((int64_t)P * H < ((int64_t)1 << 31) && n < ((int64_t)1 << 31), "photons: frame size out of range");
@@ -276,7 +277,7 @@ void launch_photons(const FramePtrs& fp, int nframes, int P, int H, int W, float
   check(cnt != 0 && psum != 0 && occ != 0 && aligned16(cnt) && aligned16(psum) && aligned16(occ),
         "photons: accumulators must be non-null and 16-B aligned");
   check(pk != 0 && tot != 0 && pk % 4 == 0 && tot % 8 == 0, "photons: pk / tot must be non-null and aligned");
-  for (int f = 0; f < nframes; ++f) check(fp.in[f] != 0 && aligned16(fp.in[f]), "photons: frames must be 16-B aligned");
+  check_frames(fp, nframes, "photons");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hip_check(hipMemsetAsync(reinterpret_cast<void*>(pk), 0, (size_t)nframes * n_roi * 8 * 4, st), "photons clear pk");
   hip_check(hipMemsetAsync(reinterpret_cast<void*>(tot), 0, (size_t)nframes * n_roi * 8, st), "photons clear tot");

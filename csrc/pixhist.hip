@@ -57,6 +57,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace pr {
 
@@ -224,7 +225,7 @@ int pixel_hist_tile_pixels(int nbins) {
 
 void launch_pixel_hist(const FramePtrs& fp, int nframes, int64_t n, float lo, float hi, float inv_w, int nbins,
                        uint64_t hist, uint64_t stream, int layout) {
-  check(nframes >= 1 && nframes <= kMaxFrames, "pixel_hist: nframes out of range");
+  check_nframes(nframes, "pixel_hist");
   check(nbins >= 1 && nbins <= kHistMaxBins, "pixel_hist: nbins outside [1, 1024]");
   check(n >= 1 && n < (int64_t)1 << 31 && n * (int64_t)nbins < (int64_t)1 << 31,
         "pixel_hist: n * nbins must stay below 2^31");
@@ -232,8 +233,7 @@ void launch_pixel_hist(const FramePtrs& fp, int nframes, int64_t n, float lo, fl
   check(std::isfinite(inv_w) && inv_w > 0.0f, "pixel_hist: the scale must be finite and positive");
   check(hist != 0 && aligned16(hist), "pixel_hist: hist must be non-null and 16-B aligned");
   check(layout >= 0 && layout <= 2, "pixel_hist: layout 0, 1 or 2");
-  for (int f = 0; f < nframes; ++f)
-    check(fp.in[f] != 0 && aligned16(fp.in[f]), "pixel_hist: frames must be 16-B aligned");
+  check_frames(fp, nframes, "pixel_hist");
   const int T = pixel_hist_tile_pixels(nbins);
   HistParams hp;
   hp.lo = lo;

@@ -16,19 +16,15 @@
 // The callers hold Q = ceil(max(|vmin|, |vmax|) * 2^S) below 2^31 (q fits an int32) and a run at or
 // below min(2^31 - 1, (2^63 - 1) / Q^2) frames, so no word overflows.  The kernel never clears anything.
 //
-// MI355X design: a lane owns 4 consecutive pixels (one 16-B non-temporal load per frame), one owner
-// per pixel per launch, so no atomics.  A frame's class is the same for the whole grid: every wave
-// reads the (at most 64) keys with ONE load, lane f taking keys[f], and a ballot turns them into a
-// 64-bit frame mask per class that lives in scalar registers.  The lane then makes one PASS per class
-// over that class's frames only -- the frame indices come off the mask with scalar bit operations,
-// the frame pointers with scalar loads from the kernel arguments -- with 8 (then 4, then 1) loads in
-// flight, ONE set of partials in registers, and after the pass ONE read-modify-write of the lane's
-// words of that class: 16-B accesses where the plane is 16-B aligned (cnt / qmax / above: one each,
-// sum / sq: two each).  A class without a frame in the launch has an empty mask: its pass is skipped
-// on a scalar branch and its words are neither read nor written (in steady state most batches are all
-// misses: half the accumulator traffic).  The planes of class 1 start at n elements, 16-B aligned iff
-// n % 4 == 0; otherwise its words go one by one, as K-09 does for candidates >= 1.  The n % 4 last
-// pixels of a frame go to one extra lane that walks them with scalar accesses.
+// MI355X design: the owner-lane accumulator of accum.h over 16-B float32 loads, one plane per class.
+// A frame's class is the same for the whole grid: every wave reads the (at most 64) keys with ONE
+// load, lane f taking keys[f], and a ballot turns them into a 64-bit frame mask per class that lives
+// in scalar registers.  The lane then makes one PASS per class over that class's frames only -- the
+// frame indices come off the mask with scalar bit operations, the frame pointers with scalar loads
+// from the kernel arguments -- with ONE set of partials in registers, then the read-modify-write of
+// its words of that class.  A class without a frame in the launch has an empty mask: its pass is
+// skipped on a scalar branch and its words are neither read nor written (in steady state most batches
+// are all misses: half the accumulator traffic).
 //
 // In-batch partial widths, from the 64-frame bound: cnt, above <= 64 (32-bit); |sum| <= 64 * Q < 2^37
 // (64-bit); sq <= 64 * Q^2, which the run bound keeps below 2^63 for ANY accepted Q (2^50 at the
@@ -37,14 +33,11 @@
 // Compiler's resource usage (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage):
 // powder_kernel: 74 VGPRs, 102 SGPRs, no scratch memory (0 bytes per lane, no spills), no LDS, occupancy
 // 6 waves per SIMD.  The frame pointers come by s_load_dwordx2, the frames by global_load_dwordx4 nt.
-#include <cmath>
-
-#include "common.h"
+#include "accum.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace pr {
-
-typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
 
 struct PowParams {
   float vmin, vmax, scale, thr;   // scale = 2^S
@@ -99,17 +92,6 @@ __device__ __forceinline__ int pow_next(uint64_t& m) {
   return f;
 }
 
-// K frames of the mask with K loads in flight
-template <int K>
-__device__ __forceinline__ void pow_group(PowPart<4>& a, const FramePtrs& fp, uint64_t& m, const int64_t q,
-                                          const PowParams& pp) {
-  f32x4_t r[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) r[k] = ld_nt_f4(gin<f32x4_t>(fp.in[pow_next(m)]) + q);
-#pragma unroll
-  for (int k = 0; k < K; ++k) pow_add4(a, r[k], pp);
-}
-
 __global__ __launch_bounds__(256) void powder_kernel(const FramePtrs fp, const int nframes, const int64_t n,
                                                      const PowParams pp, const int* __restrict__ keys,
                                                      const int key_min, long long* __restrict__ nfr,
@@ -140,42 +122,18 @@ __global__ __launch_bounds__(256) void powder_kernel(const FramePtrs fp, const i
       if (m == 0ull) continue;   // no frame of this class: its words stay as they are (scalar branch)
       PowPart<4> a;
       pow_zero(a);
-      int left = __builtin_popcountll(m);
-      for (; left >= 8; left -= 8) pow_group<8>(a, fp, m, q, pp);
-      if (left >= 4) {
-        pow_group<4>(a, fp, m, q, pp);
-        left -= 4;
-      }
-      for (; left > 0; --left) pow_group<1>(a, fp, m, q, pp);
+      acc_group<f32x4_t, true>(__builtin_popcountll(m), q, [&] { return fp.in[pow_next(m)]; },
+                               [&](const f32x4_t r) { pow_add4(a, r, pp); });
       const int64_t o = (int64_t)c * n + p0;
       if (c == 0 || vec) {
-        u32x4_t* pc = reinterpret_cast<u32x4_t*>(cnt + o);
-        u32x4_t* pa = reinterpret_cast<u32x4_t*>(above + o);
-        u32x4_t* pm = reinterpret_cast<u32x4_t*>(qmax + o);
-        u64x2_t* ps = reinterpret_cast<u64x2_t*>(sum + o);
-        u64x2_t* pq = reinterpret_cast<u64x2_t*>(sq + o);
-        u32x4_t vc = *pc, va = *pa, vm = *pm;
-        u64x2_t s0 = ps[0], s1 = ps[1], q0 = pq[0], q1 = pq[1];
-        vc.x += a.cnt[0]; vc.y += a.cnt[1]; vc.z += a.cnt[2]; vc.w += a.cnt[3];
-        va.x += a.above[0]; va.y += a.above[1]; va.z += a.above[2]; va.w += a.above[3];
-        vm.x = (uint32_t)max((int32_t)vm.x, a.qmax[0]); vm.y = (uint32_t)max((int32_t)vm.y, a.qmax[1]);
-        vm.z = (uint32_t)max((int32_t)vm.z, a.qmax[2]); vm.w = (uint32_t)max((int32_t)vm.w, a.qmax[3]);
-        // two's complement: the unsigned 64-bit add of a signed partial is the signed add
-        s0.x += (unsigned long long)a.sum[0]; s0.y += (unsigned long long)a.sum[1];
-        s1.x += (unsigned long long)a.sum[2]; s1.y += (unsigned long long)a.sum[3];
-        q0.x += a.sq[0]; q0.y += a.sq[1]; q1.x += a.sq[2]; q1.y += a.sq[3];
-        *pc = vc; *pa = va; *pm = vm;
-        ps[0] = s0; ps[1] = s1;
-        pq[0] = q0; pq[1] = q1;
+        Words32 wc, wa, wm;
+        Words64 ws, wq;
+        wc.load(cnt + o); wa.load(above + o); wm.load(qmax + o); ws.load(sum + o); wq.load(sq + o);
+        wc.add(a.cnt); wa.add(a.above); wm.smax(a.qmax); ws.add(a.sum); wq.add(a.sq);
+        wc.store(cnt + o); wa.store(above + o); wm.store(qmax + o); ws.store(sum + o); wq.store(sq + o);
       } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          cnt[o + i] += (int32_t)a.cnt[i];
-          above[o + i] += (int32_t)a.above[i];
-          qmax[o + i] = max(qmax[o + i], a.qmax[i]);
-          sum[o + i] += a.sum[i];
-          sq[o + i] += a.sq[i];
-        }
+        acc_add(cnt + o, a.cnt); acc_add(above + o, a.above); acc_max(qmax + o, a.qmax);
+        acc_add(sum + o, a.sum); acc_add(sq + o, a.sq);
       }
     }
   } else if (q == nq) {
@@ -189,11 +147,8 @@ __global__ __launch_bounds__(256) void powder_kernel(const FramePtrs fp, const i
         pow_zero(a);
         while (m != 0ull) pow_add<1, 0>(a, gin<float>(fp.in[pow_next(m)])[p], pp);
         const int64_t o = (int64_t)c * n + p;
-        cnt[o] += (int32_t)a.cnt[0];
-        above[o] += (int32_t)a.above[0];
-        qmax[o] = max(qmax[o], a.qmax[0]);
-        sum[o] += a.sum[0];
-        sq[o] += a.sq[0];
+        acc_add(cnt + o, a.cnt); acc_add(above + o, a.above); acc_max(qmax + o, a.qmax);
+        acc_add(sum + o, a.sum); acc_add(sq + o, a.sq);
       }
     }
   }
@@ -202,16 +157,10 @@ __global__ __launch_bounds__(256) void powder_kernel(const FramePtrs fp, const i
 void launch_powder(const FramePtrs& fp, int nframes, int64_t n, float vmin, float vmax, int frac_bits,
                    float thr_above, int nc, uint64_t keys, int key_min, uint64_t nfr, uint64_t cnt, uint64_t sum,
                    uint64_t sq, uint64_t qmax, uint64_t above, uint64_t stream) {
-  check(nframes >= 1 && nframes <= kMaxFrames, "powder: nframes out of range");
-  check(n >= 1 && n < (int64_t)1 << 31, "powder: frame size out of range");
-  check(std::isfinite(vmin) && std::isfinite(vmax) && vmin <= vmax, "powder: the value window must be finite and ordered");
-  check(frac_bits >= 0 && frac_bits <= 16, "powder: frac_bits outside [0, 16]");
+  check_nframes(nframes, "powder");
+  check_frame_size(n, "powder");
+  const float scale = quant_bound(vmin, vmax, frac_bits, nframes, "powder");
   check(thr_above == thr_above, "powder: thr_above is NaN");
-  // Q = ceil(max(|vmin|, |vmax|) * 2^S) in doubles: a float32 times 2^16 is exact
-  const double Q = std::ceil(std::ldexp(std::max(std::fabs((double)vmin), std::fabs((double)vmax)), frac_bits));
-  check(Q < 2147483648.0, "powder: max(|vmin|, |vmax|) * 2^frac_bits must stay below 2^31");
-  const unsigned __int128 q2 = (unsigned __int128)(uint64_t)Q * (uint64_t)Q;
-  check(q2 * (unsigned)nframes <= (unsigned __int128)INT64_MAX, "powder: more frames than (2^63 - 1) / Q^2");
   check(nc == 1 || nc == 2, "powder: 1 or 2 classes");
   check((nc == 2) == (keys != 0), "powder: keys are given iff there are 2 classes");
   check(keys % 4 == 0, "powder: keys must be 4-B aligned");
@@ -219,11 +168,9 @@ void launch_powder(const FramePtrs& fp, int nframes, int64_t n, float vmin, floa
   check(cnt != 0 && sum != 0 && sq != 0 && qmax != 0 && above != 0 && aligned16(cnt) && aligned16(sum) &&
             aligned16(sq) && aligned16(qmax) && aligned16(above),
         "powder: accumulators must be non-null and 16-B aligned");
-  for (int f = 0; f < nframes; ++f) check(fp.in[f] != 0 && aligned16(fp.in[f]), "powder: frames must be 16-B aligned");
-  const int64_t lanes = n / 4 + (n % 4 != 0 ? 1 : 0);
-  const dim3 grid((unsigned)((lanes + 255) / 256));
-  const PowParams pp{vmin, vmax, std::ldexp(1.0f, frac_bits), thr_above};
-  hipLaunchKernelGGL(powder_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), fp, nframes, n, pp,
+  check_frames(fp, nframes, "powder");
+  const PowParams pp{vmin, vmax, scale, thr_above};
+  hipLaunchKernelGGL(powder_kernel, owner_lane_grid(n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), fp, nframes, n, pp,
                      reinterpret_cast<const int*>(keys), key_min, reinterpret_cast<long long*>(nfr),
                      reinterpret_cast<int32_t*>(cnt), reinterpret_cast<long long*>(sum),
                      reinterpret_cast<unsigned long long*>(sq), reinterpret_cast<int32_t*>(qmax),

@@ -52,10 +52,9 @@
 // cost more than the collisions it removes (about 1.1 us/frame slower even where nothing collides).
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 #include <cmath>
-#include <map>
-#include <mutex>
 
 #include <algorithm>
 
@@ -227,29 +226,10 @@ __global__ __launch_bounds__(256) void radial_finalize_kernel(const unsigned lon
   }
 }
 
-// resident workgroups of the 256-thread kernel with `lds` bytes of dynamic LDS on the CURRENT
-// device, queried once per (device, lds) under a lock (speed only: grid sizing)
-template <typename Kern>
-static int rad_resident_blocks(Kern k, int lds) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, int> cache;
-  int dev = 0;
-  hip_check(hipGetDevice(&dev), "radial device");
-  std::lock_guard<std::mutex> lk(mu);
-  int& n = cache[{dev, lds}];
-  if (n == 0) {
-    int cus = 0, per = 0;
-    hip_check(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "radial cu count");
-    hip_check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)k, 256, (size_t)lds), "radial occupancy");
-    n = std::max(1, cus * std::max(1, per));
-  }
-  return n;
-}
-
 void launch_radial(const FramePtrs& fp, int nframes, int64_t n, uint64_t bins, int nbins, float vmin, float vmax,
                    int frac_bits, uint64_t sums, uint64_t counts, uint64_t profile, uint64_t run, uint64_t stream) {
-  check(nframes >= 1 && nframes <= kMaxFrames, "radial: nframes out of range");
-  check(n >= 1 && n < (int64_t)1 << 31, "radial: frame size out of range");
+  check_nframes(nframes, "radial");
+  check_frame_size(n, "radial");
   check(nbins >= 1 && nbins <= kRadMaxBins, "radial: nbins must be in [1, 4096]");
   check(frac_bits >= 0 && frac_bits <= 60, "radial: frac_bits out of range");
   check(vmin <= vmax, "radial: empty value window");
@@ -261,7 +241,7 @@ void launch_radial(const FramePtrs& fp, int nframes, int64_t n, uint64_t bins, i
   check(sums % 8 == 0 && counts % 4 == 0 && profile % 4 == 0 && run % 8 == 0 && sums != 0 && counts != 0 &&
             profile != 0,
         "radial: misaligned or missing output");
-  for (int f = 0; f < nframes; ++f) check(fp.in[f] != 0 && aligned16(fp.in[f]), "radial: frames must be 16-B aligned");
+  check_frames(fp, nframes, "radial");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   RadParams rp{vmin, vmax, std::ldexp(1.0f, frac_bits), nbins, 1, n, bins};
   while (rp.copies < kRadMaxCopies && 2 * rp.copies * nbins * 12 <= kRadLdsBytes) rp.copies *= 2;
@@ -269,7 +249,7 @@ void launch_radial(const FramePtrs& fp, int nframes, int64_t n, uint64_t bins, i
   const int64_t n4 = n / 4;
   const int64_t chunks = std::max<int64_t>(1, (n4 + 256 * kRadK - 1) / (256 * kRadK)) * nframes;
   auto kern = radial_kernel;
-  const int g = (int)std::min<int64_t>(chunks, rad_resident_blocks(kern, lds));
+  const int g = (int)std::min<int64_t>(chunks, resident_blocks((const void*)kern, lds, "radial"));
   unsigned long long* S = reinterpret_cast<unsigned long long*>(sums);
   unsigned int* C = reinterpret_cast<unsigned int*>(counts);
   hip_check(hipMemsetAsync(S, 0, (size_t)nframes * nbins * 8, s), "radial clear sums");

@@ -60,6 +60,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace pr {
 
@@ -320,7 +321,7 @@ RoiPlan::~RoiPlan() {
 
 void launch_roi(const FramePtrs& fp, int nframes, const RoiPlan& plan, float vmin, float vmax, int frac_bits,
                 uint64_t mask, uint64_t rows, uint64_t projx, uint64_t projy, uint64_t stream) {
-  check(nframes >= 1 && nframes <= kMaxFrames, "roi: nframes out of range");
+  check_nframes(nframes, "roi");
   check(plan.strips != 0 && plan.nstrips >= 1, "roi: empty plan");
   check(std::isfinite(vmin) && std::isfinite(vmax) && vmin <= vmax, "roi: the value window must be finite, vmin <= vmax");
   check(frac_bits >= 0 && frac_bits <= 16, "roi: frac_bits must be in [0, 16]");
@@ -337,7 +338,7 @@ void launch_roi(const FramePtrs& fp, int nframes, const RoiPlan& plan, float vmi
   check(rows != 0 && rows % 64 == 0, "roi: rows must be non-null and 64-B aligned");
   check(projx % 8 == 0 && projy % 8 == 0, "roi: projections must be 8-B aligned");
   check(mask % 16 == 0, "roi: the mask must be 16-B aligned");
-  for (int f = 0; f < nframes; ++f) check(fp.in[f] != 0 && aligned16(fp.in[f]), "roi: frames must be 16-B aligned");
+  check_frames(fp, nframes, "roi");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hip_check(hipMemsetAsync(reinterpret_cast<void*>(rows), 0, (size_t)nframes * plan.R * 64, st), "roi clear rows");
   if (projx != 0)

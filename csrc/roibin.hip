@@ -59,6 +59,7 @@
 // No A/B variants were run.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 #include <cmath>
 
@@ -366,7 +367,7 @@ void launch_roibin(const FramePtrs& fp, int nframes, int P, int H, int W, int B,
                    uint64_t npk, uint64_t nbox, uint64_t nbad, uint64_t nsat, uint64_t flags, uint64_t offs,
                    uint64_t ctr, uint64_t rec, uint64_t box, uint64_t stream, int phases) {
   check(phases >= 1 && phases <= 3, "roibin: phases must be 1 (bin), 2 (boxes) or 3");
-  check(nframes >= 1 && nframes <= kMaxFrames, "roibin: nframes out of range");
+  check_nframes(nframes, "roibin");
   check(P >= 1 && H >= 1 && W >= 1 && (int64_t)P * H * W < (int64_t)1 << 31, "roibin: frame shape out of range");
   check(B == 1 || B == 2 || B == 4, "roibin: bin must be 1, 2 or 4");
   check(R >= 0 && R <= kRoibinMaxRadius, "roibin: box radius out of range");
@@ -382,7 +383,7 @@ void launch_roibin(const FramePtrs& fp, int nframes, int P, int H, int W, int B,
             npk % 4 == 0 && nbox % 4 == 0 && nbad % 4 == 0 && nsat % 4 == 0 && offs % 8 == 0 && ctr % 4 == 0 &&
             rec % 4 == 0 && box % 4 == 0,
         "roibin: misaligned or missing output");
-  for (int f = 0; f < nframes; ++f) check(fp.in[f] != 0 && aligned16(fp.in[f]), "roibin: frames must be 16-B aligned");
+  check_frames(fp, nframes, "roibin");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   RbParams rp{};
   rp.inv = inv; rp.vmin = vmin; rp.vmax = vmax;

@@ -47,11 +47,10 @@
 // cost 0.05 more).
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <cmath>
-#include <map>
-#include <mutex>
 
 namespace pr {
 
@@ -315,37 +314,18 @@ static int64_t sp_dir_bytes(int64_t n, int frames) {
 }
 
 int64_t sparsify_scratch_bytes(int64_t n, int64_t cap, int frames) {
-  check(n >= 1 && n < (int64_t)1 << 31, "sparsify: frame size out of range");
-  check(frames >= 1 && frames <= kMaxFrames, "sparsify: nframes out of range");
+  check_frame_size(n, "sparsify");
+  check_nframes(frames, "sparsify");
   check(cap >= 1 && cap * frames < (int64_t)1 << 31, "sparsify: cap out of range");
   return kSparseScratchHeader + sp_dir_bytes(n, frames) + (int64_t)frames * cap * 8;
-}
-
-// resident workgroups of the scan kernel on the CURRENT device, queried once per device under a
-// lock (speed only: grid sizing)
-static int sp_resident_blocks() {
-  static std::mutex mu;
-  static std::map<int, int> cache;
-  int dev = 0;
-  hip_check(hipGetDevice(&dev), "sparsify device");
-  std::lock_guard<std::mutex> lk(mu);
-  int& n = cache[dev];
-  if (n == 0) {
-    int cus = 0, per = 0;
-    hip_check(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "sparsify cu count");
-    hip_check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)sparse_scan_kernel, 256, 0),
-              "sparsify occupancy");
-    n = std::max(1, cus * std::max(1, per));
-  }
-  return n;
 }
 
 void launch_sparsify(const FramePtrs& fp, int nframes, int64_t n, float thr, float vmax, int64_t cap, uint64_t mask,
                      uint64_t keys, int key_min, uint64_t nnz, uint64_t flags, uint64_t offs, uint64_t pix,
                      uint64_t val, uint64_t scratch, int64_t scratch_bytes, uint64_t stream, int phases) {
   check(phases >= 1 && phases <= 3, "sparsify: phases must be 1 (scan), 2 (pack) or 3");
-  check(nframes >= 1 && nframes <= kMaxFrames, "sparsify: nframes out of range");
-  check(n >= 1 && n < (int64_t)1 << 31, "sparsify: frame size out of range");
+  check_nframes(nframes, "sparsify");
+  check_frame_size(n, "sparsify");
   check(cap >= 1 && cap * nframes < (int64_t)1 << 31, "sparsify: cap must be >= 1 and F * cap < 2^31");
   check(std::isfinite(thr) && std::isfinite(vmax) && thr <= vmax, "sparsify: the value window must be finite, thr <= vmax");
   check(mask % 4 == 0 && keys % 4 == 0, "sparsify: mask / keys must be 4-B aligned");
@@ -354,7 +334,7 @@ void launch_sparsify(const FramePtrs& fp, int nframes, int64_t n, float thr, flo
         "sparsify: misaligned or missing output");
   check(scratch != 0 && scratch % 16 == 0, "sparsify: the scratch block must be 16-B aligned");
   check(scratch_bytes >= sparsify_scratch_bytes(n, cap, nframes), "sparsify: scratch block too small");
-  for (int f = 0; f < nframes; ++f) check(fp.in[f] != 0 && aligned16(fp.in[f]), "sparsify: frames must be 16-B aligned");
+  check_frames(fp, nframes, "sparsify");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int ncpf = (int)sp_chunks_per_frame(n);
   SpParams sp{thr, vmax, (int)cap, key_min, n, mask, keys, 0, 0, 0, 0};
@@ -365,7 +345,7 @@ void launch_sparsify(const FramePtrs& fp, int nframes, int64_t n, float thr, flo
   if (phases & 1) {
     hip_check(hipMemsetAsync(reinterpret_cast<void*>(scratch), 0, kSparseScratchHeader, s), "sparsify clear cursors");
     const int64_t chunks = (int64_t)ncpf * nframes;
-    const int g = (int)std::min<int64_t>(chunks, sp_resident_blocks());
+    const int g = (int)std::min<int64_t>(chunks, resident_blocks((const void*)sparse_scan_kernel, 0, "sparsify"));
     hipLaunchKernelGGL(sparse_scan_kernel, dim3(g), dim3(256), 0, s, fp, sp, nframes);
     hip_check(hipGetLastError(), "sparsify scan launch");
   }
